@@ -9,12 +9,14 @@ before the timed region.  --dtype selects the arithmetic of the matrix-core prod
 (bf16 MFMA operands AND bf16 storage of what the fused block kernels save for their backward / the weight gradients; fp32
 accumulation / residual stream / LayerNorm / softmax / loss / master weights).
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5                  (the headline line alone)
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full           (+ roofline leg, stock loop, CPU baseline)
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   (+ the last timed step's loss as DIR/loss.npy)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
   ... bench.py --gpus 2 --dist-backend gloo    (plumbing check on a ONE-GPU box: both ranks share cuda:0, collectives over gloo on
                                                 device tensors -- the engine path is the RCCL one; the JSON says so)
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields, incl. `roofline` and `cpu_baseline`).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields, incl. `roofline` and `cpu_baseline` of --full).
 Every rank runs every leg (timed region, roofline leg) so no rank leaves while another still has a collective to issue.
 """
 import argparse
@@ -112,19 +114,49 @@ def host_cpu():
     return model, (len(cores) or logical), logical
 
 
+def usable_cpus():
+    """CPUs this process may keep busy: its affinity mask, capped by a cgroup v2 CPU quota and by OMP_NUM_THREADS when either is
+    set (on a shared host both can be far below the core count, and a thread pool sized past them only slows itself down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        with open("/sys/fs/cgroup/cpu.max") as f:
+            quota, period = f.read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, -(-int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return n
+
+
+def dump_outputs(out_dir, loss):
+    """--dump-outputs: what the last timed step returned to its caller (TrainEngine.step: the loss of the batch) as
+    out_dir/loss.npy, float32.  The updated parameters and their gradients are not written: the weight-gradient reductions
+    accumulate with floating-point atomics in run-dependent order, and Adam's m / sqrt(v) turns those last-bit differences of
+    near-zero gradients into +-lr steps, so they differ from run to run by far more than rounding."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), torch.as_tensor(loss).detach().float().reshape(-1).cpu().numpy())
+
+
 def cpu_baseline(vol, timed=5, budget_s=420.0, batches=(2, 1), warmups=2):
-    """the CPU restatement (oracle/, kind 'port') timed on ALL PHYSICAL host cores: the identical train
-    step (fwd + MDiceLoss + bwd + Adam, fp32) of the base model on full-size CT+MR pairs.  Protocol = BASELINE.md's: `warmups`
-    (2) untimed full-size steps, then `timed` (5) timed steps, median -- at B = 2, the batch the GPU value is quoted on (a step is
-    ~40 s on 128 cores, so that alone is ~4.5 min).  B = 1 follows with whatever is left of `budget_s` (up to 3 timed steps, the
-    pools are warm by then; it was the slower one in pairs/s on every box so far).  `value` is the better batch size in pairs/s (the
-    unit the GPU value counts).  Bounded: timing stops early (and says so) once `budget_s` of CPU work is spent."""
+    """the CPU restatement (oracle/, kind 'port') timed on the physical host cores this process may use (all
+    of them unless an affinity mask, a CPU quota or OMP_NUM_THREADS allows fewer -- see usable_cpus): the identical train step
+    (fwd + MDiceLoss + bwd + Adam, fp32) of the base model on full-size CT+MR pairs.  Protocol = BASELINE.md's: `warmups` (2)
+    untimed full-size steps, then `timed` (5) timed steps, median -- at B = 2, the batch the GPU value is quoted on (a step took
+    ~45 s on 128 threads of the 2 x 64-core host, 4.6 s on 16 threads under a 16-CPU quota).  B = 1 follows with whatever is left
+    of `budget_s` (up to 3 timed steps, the pools are warm by then; it was the slower one in pairs/s on every box so far).  `value`
+    is the better batch size in pairs/s (the unit the GPU value counts).  Bounded: timing stops early (and says so) once `budget_s`
+    of CPU work is spent."""
     import statistics
     import torch
     from oracle import micformer_ref as R
     from oracle.shapes import filled_params
     model, phys, logical = host_cpu()
-    threads = max(1, phys)
+    threads = max(1, min(phys, usable_cpus()))
     torch.set_num_threads(threads)
     cfg = R.Cfg()
     g = torch.Generator().manual_seed(1234)
@@ -159,9 +191,9 @@ def cpu_baseline(vol, timed=5, budget_s=420.0, batches=(2, 1), warmups=2):
     return {"value": best, "unit": "pairs/s", "cores": threads, "kind": "port", "cpu_model": model,
             "physical_cores": phys, "logical_cpus": logical, "by_batch": {f"B={b}": v for b, v in per_batch.items()},
             "sample": f"full fp32 train steps (fwd+loss+bwd+Adam, lr 1e-4, cosine per iteration) of MicFormer base on {vol[0]}^3 CT+MR "
-                      f"pairs, oracle/ torch CPU ops on {threads} threads (= physical cores of {model}); {warmups} untimed full-size "
-                      f"warm-up steps, then median of {timed} timed steps at B={batches[0]} (BASELINE.md section 3), then up to 3 timed "
-                      f"steps at the other batch size within the {budget_s:.0f} s budget; value = the better pairs/s"
+                      f"pairs, oracle/ torch CPU ops on {threads} threads (= the physical cores of {model} this process may use); "
+                      f"{warmups} untimed full-size warm-up steps, then median of {timed} timed steps at B={batches[0]} (BASELINE.md "
+                      f"section 3), then up to 3 timed steps at the other batch size within the {budget_s:.0f} s budget; value = the better pairs/s"
                       + ("; " + "; ".join(notes) if notes else "")}
 
 
@@ -301,11 +333,16 @@ def main(argv=None):
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a captured HIP graph")
     ap.add_argument("--segmented", action="store_true", help="capture the step as a sequence of HIP graphs replayed on two streams "
                     "with explicit events (main chain / parameter-gradient batches) instead of ONE graph")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement, also run the legs it does not need: the roofline leg, the stock loop "
+                         "(--gpus 1) and the CPU baseline (--gpus 1); --no-roofline / --no-stock-loop / --no-cpu-baseline drop one")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to its caller (the loss) as DIR/loss.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--stock-loop", dest="stock_loop", action="store_true", default=None,
-                    help="also time the reference's literal loop body (stock torch.optim.Adam + CosineAnnealingLR, eager) on the drop-in "
-                         "modules: extra keys stock_loop_pairs_per_s / stock_loop (default: on for --gpus 1)")
+                    help="--full: also time the reference's literal loop body (stock torch.optim.Adam + CosineAnnealingLR, eager) on the "
+                         "drop-in modules: extra keys stock_loop_pairs_per_s / stock_loop (default: on for --gpus 1)")
     ap.add_argument("--no-stock-loop", dest="stock_loop", action="store_false")
     ap.add_argument("--stock-steps", type=int, default=5)
     ap.add_argument("--no-profile-gate", action="store_true",
@@ -442,6 +479,9 @@ def main(argv=None):
     probe = os.environ.get("MICF_SEG_SKIP_SIDE") == "1"             # timing probe: main chain alone, parameter gradients skipped
     assert probe or loss_val == loss_val, "loss is NaN"
     ms_step = 1000.0 * dt / args.steps
+    if args.dump_outputs and rank == 0:
+        # (before the roofline leg: its eager steps update the weights again)
+        dump_outputs(args.dump_outputs, loss)
 
     out = {
         "metric": "train volumes/sec (128^3 CT+MRI pair)", "value": round(world * args.batch * args.steps / dt, 4),
@@ -485,7 +525,7 @@ def main(argv=None):
 
     # ---- roofline leg: HIP events around every C-ABI launch of 2 eager steps on the launch stream(s), keyed by (entry point,
     # shape).  EVERY rank runs it (the eager steps contain the gradient all-reduce); rank 0 reports its own numbers.
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         nprof = 2
         gate_cycles = 0
         eng_graph = eng.use_graph
@@ -666,15 +706,15 @@ def main(argv=None):
                                "whole_step_TFLOP/s": round(tot_f / nprof / (ms_step * 1e-3) / 1e12, 2),
                                "whole_step_GB/s": round(tot_b / nprof / (ms_step * 1e-3) / 1e9, 1)}
 
-    if (args.stock_loop if args.stock_loop is not None else (world == 1 and not forced)) and not stub and not live_group:
+    if args.full and (args.stock_loop if args.stock_loop is not None else (world == 1 and not forced)) and not stub and not live_group:
         # (one GPU only: the stock loop has no gradient exchange; the engine's flat buffers stay alive beside it -- ~6 GB + ~6 GB)
         sl = stock_loop(args.embed_dim, depths, not args.eval_mode, x, tgt, args.stock_steps, 2)
         out["stock_loop_pairs_per_s"] = sl["pairs_per_s"]
         out["stock_loop"] = sl
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1 and not stub:
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub:
             out["cpu_baseline"] = cpu_baseline(vol, timed=args.cpu_steps, budget_s=args.cpu_budget_s)
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if live_group:

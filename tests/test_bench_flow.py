@@ -38,7 +38,7 @@ def _is_unit_roofline(roof):
 
 
 def test_bench_two_ranks_complete_with_roofline_leg():
-    r = _run(2)
+    r = _run(2, ("--full",))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout                       # exactly one JSON line, from rank 0
@@ -61,10 +61,27 @@ def test_bench_single_process_stub_and_no_roofline():
 
 
 @pytest.mark.timeout(300)
+def test_plain_bench_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is set-up, warm-up, the timed steps and the result line: no roofline leg, stock loop or CPU
+    baseline (two ranks here, so the leg every rank joins is left out on all of them).  --dump-outputs writes the loss of the
+    last timed step."""
+    r = _run(2, ("--dump-outputs", str(tmp_path)))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["unit"] == "pairs/s" and out["higher_is_better"] is True
+    assert not {"roofline", "kernels", "cpu_baseline", "stock_loop"} & set(out)
+    import numpy as np
+    loss = np.load(tmp_path / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,) and abs(float(loss[0]) - out["final_loss"]) < 1e-6
+
+
+@pytest.mark.timeout(300)
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus N` with NO launcher in the command (the form the driver types for N = 1) starts
     its N ranks itself: one JSON line from rank 0, rc 0."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-stub"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-stub", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=dict(env, OMP_NUM_THREADS="1"), cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -99,7 +116,7 @@ def test_self_launched_bench_two_ranks_on_one_gpu():
     """The self-launched form with the REAL engine: `python bench.py --gpus 2 --dist-backend gloo` (no torchrun), both ranks on the
     box's one MI355X: base / 128^3 / local batch 2 / bf16, capture under a live group, replays with the per-slice all-reduces."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dist-backend", "gloo",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
@@ -119,7 +136,7 @@ def test_bench_nccl_branch_with_one_rank():
     slice all-reduced for real over the bf16 wire, the collectives of the timing / identification legs, destroy_process_group --
     everything the 8-GPU run does except the second device."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--force-dist",
-           "--dist-backend", "nccl", "--no-cpu-baseline"]
+           "--dist-backend", "nccl", "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
@@ -138,7 +155,7 @@ def test_bench_real_engine_two_ranks_on_one_gpu():
     workload (base, 128^3, local batch 2, bf16), 3 steps."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--dist-backend", "gloo", "--no-cpu-baseline"]
+           "--dist-backend", "gloo", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
@@ -159,7 +176,7 @@ def test_bench_real_engine_four_ranks_on_one_gpu():
     one JSON line, and the loss is the 4-rank data-parallel step's (finite, below the initial 0.75)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-           "--vol", "64", "--dtype", "fp32", "--dist-backend", "gloo", "--no-cpu-baseline"]
+           "--vol", "64", "--dtype", "fp32", "--dist-backend", "gloo", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
@@ -189,3 +206,22 @@ def test_bench_eight_ranks_on_one_gpu():
     assert out["n_gpus"] == 8 and out["rccl_ranks"] == 8 and out["distinct_local_devices"] == 1 and out["grad_wire"] == "bf16"
     assert out["config"]["global_batch"] == 16 and out["config"]["parallelism"] == "dp8" and out["dtype"] == "bf16"
     assert 0.0 < out["final_loss"] < 0.8 and out["value"] > 0 and "roofline" not in out
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(900)
+def test_plain_bench_dumps_the_last_timed_step(tmp_path):
+    """The plain one-GPU run with --dump-outputs: the result line carries the headline fields only, and DIR holds what the last
+    timed step returned, its loss (float32)."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--vol", "64",
+           "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=env, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["dtype"] == "bf16" and 0.0 < out["final_loss"] < 2.0
+    assert not {"roofline", "kernels", "cpu_baseline", "stock_loop"} & set(out)
+    import numpy as np
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["loss.npy"]
+    loss = np.load(tmp_path / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == (1,) and abs(float(loss[0]) - out["final_loss"]) < 1e-6

@@ -325,14 +325,14 @@ def test_forward_after_engine_steps_uses_the_updated_weights(M, dtype):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_training_script_in_miniature(dtype):
+def test_training_script_in_miniature(dtype, tmp_path):
     """tools/train_synthetic.py end to end on the fused kernels' widths (embed 48): train with the graph engine, validate by
     sliding-window inference + argmax meandice, save / resume a checkpoint.  Its own assertions: the validation loss falls and
     the resumed model validates exactly like the trained one (this is what caught stale weight copies after engine steps)."""
     import json, subprocess, sys
     tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "train_synthetic.py")
     r = subprocess.run([sys.executable, tool, "--dtype", dtype, "--embed-dim", "48", "--vol", "64", "--steps", "60",
-                        "--out", f"/tmp/micf_test_{dtype}.pth.tar"], capture_output=True, text=True, timeout=600)
+                        "--out", str(tmp_path / f"micf_test_{dtype}.pth.tar")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["val_loss"][1] < out["val_loss"][0] and abs(out["resumed_val_meandice"] - out["val_meandice"][1]) < 1e-3

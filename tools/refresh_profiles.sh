@@ -5,8 +5,8 @@ set -u
 R=${1:-r04}
 OUT=gpurun_out/$R
 mkdir -p $OUT
-python bench.py > $OUT/${R}_bench.json 2> $OUT/bench.err
-python bench.py --dtype fp32 --no-cpu-baseline --no-stock-loop > $OUT/${R}_bench_fp32.json 2>> $OUT/bench.err
+python bench.py --full > $OUT/${R}_bench.json 2> $OUT/bench.err
+python bench.py --full --dtype fp32 --no-cpu-baseline --no-stock-loop > $OUT/${R}_bench_fp32.json 2>> $OUT/bench.err
 # the step as a sequence of graphs on two streams (opt-in layout), its main chain alone and everything serial: how much of the
 # parameter-gradient side work is hidden (functional.StepSegmenter; MICF_SEG_SKIP_SIDE computes WRONG updates: a timing probe only)
 {
