@@ -1,0 +1,187 @@
+"""On-device head of the reference's input pipeline: raw CT / MR volumes (and the CT label volume) of a sample -> the float16
+(2, D, H, W) image, the uint8 class map and `crop_indexes` that MMWHS_noCrop_Augment.__getitem__ produces on the CPU
+(MMWHS.py:308-405, image_utils.py:48-55), on the HIP kernels of csrc/volume_loader.hip.
+
+    from micformer_amd import data, loader
+    ct, mr, lab = (torch.from_numpy(a).cuda(non_blocking=True) for a in (ct_arr, mr_arr, ct_label_arr))   # any (d, h, w) each
+    image, label_map, crop = loader.load_batch([(ct, mr, lab), ...])        # fp16 [B,2,128,128,128], uint8 [B,128,128,128], int32 [B,3,2]
+    x, y = data.prepare_raw_batch(image, label_map, params)                 # the device-side tail; y feeds MDiceLoss as it is
+
+What is computed, per sample (each array is resized independently from its own shape):
+  * min-max normalisation of each image volume over the whole volume, (x - min) / (max - min), with one IEEE float32 divide per
+    element.  A constant volume gives NaN everywhere, as the reference does.  NaN in the input is out of scope.
+  * trilinear resize (align_corners=False) of the normalised volumes to `size`, float16, channel 0 = CT, channel 1 = MR.
+  * nearest resize of the CT label + lookup in `label_values` -> class map: 0 where the label is 0, k where it equals
+    label_values[k - 1], 255 elsewhere.  (The reference's MR label planes are dropped by its `label[:8]` and are not computed.)
+  * crop_indexes: per axis (max(0, min - 1), max + 1) of the voxels where resized CT + MR != 0; (0, 0) when the image is all zero
+    (the reference raises there).
+
+Two deliberate deviations from the reference: an int16 volume whose range exceeds 32767 is normalised with int32 arithmetic (the
+reference's int16 `image - min` wraps), and the label is a uint8 class map with 255 for "no plane set" instead of 8 bool planes.
+
+Nothing here synchronises with the host or runs an ATen compute op (allocation only); the launches go to the current stream and
+can be captured by torch.cuda.graph when `out` is given.  The entry points are declared in include/micformer_loader.h and bound
+from their own ctypes table (SIGNATURES below), apart from include/micformer_hip.h's.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+MMWHS_LABEL_VALUES = (205, 420, 500, 550, 600, 820, 850)          # MMWHS.py:289; class k = label_values[k - 1], class 0 = label 0
+MAX_LABEL_VALUES = 254
+DTYPE_I16, DTYPE_F32, DTYPE_I32 = 0, 1, 2
+_IMAGE_DTYPES = {torch.int16: DTYPE_I16, torch.float32: DTYPE_F32}
+_LABEL_DTYPES = {torch.int16: DTYPE_I16, torch.int32: DTYPE_I32}
+
+# name -> argument signature (as _lib.SIGNATURES); the workspace query returns int64, the other int
+SIGNATURES = {
+    "micf_volume_loader_workspace": "i",
+    "micf_volume_loader": "piiiipiplpppp",
+}
+_RESTYPE = {"micf_volume_loader_workspace": _lib._L}
+
+
+class LoaderSample(ctypes.Structure):
+    """struct micf_loader_sample (include/micformer_loader.h)."""
+    _fields_ = [("ct", ctypes.c_void_p), ("mr", ctypes.c_void_p), ("label", ctypes.c_void_p),
+                ("ct_shape", ctypes.c_int32 * 3), ("mr_shape", ctypes.c_int32 * 3), ("label_shape", ctypes.c_int32 * 3),
+                ("ct_dtype", ctypes.c_int32), ("mr_dtype", ctypes.c_int32), ("label_dtype", ctypes.c_int32)]
+
+
+def _bind():
+    lib = _lib.lib
+    for name, sig in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError(f"{_lib.LIB_PATH} predates the volume loader ({name} is missing): rebuild it with "
+                              "`python -c \"import __graft_entry__ as g; g.build()\"`") from None
+        fn.argtypes = [_lib._T[c] for c in sig]
+        fn.restype = _RESTYPE.get(name, _lib._I)
+    return lib
+
+
+lib = _bind()
+
+
+def _check(name, rc):
+    if rc != 0:
+        raise _lib.MicfError(f"{name} failed: {_lib.lib.micf_strerror(rc).decode()} (code {rc})")
+
+
+def _typed(t, what, dtypes):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what} must be a tensor, got {type(t).__name__}")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{what} must be one of {sorted(str(d) for d in dtypes)}, got {t.dtype}")
+
+
+def _volume(t, what, dtypes, device):
+    if not t.is_cuda:
+        raise ValueError(f"micformer_amd.loader runs on the GPU: {what} must be a CUDA (ROCm) tensor")
+    if device is not None and t.device != device:
+        raise ValueError(f"{what} is on {t.device}, the batch on {device}")
+    if t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError(f"{what} must be a non-empty (d, h, w) volume, got shape {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what} must be contiguous")
+    return t.data_ptr(), tuple(t.shape), dtypes[t.dtype]
+
+
+def _size(size):
+    try:
+        D, H, W = (int(s) for s in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be three positive integers, got {size!r}") from None
+    if min(D, H, W) < 1:
+        raise ValueError(f"size must be three positive integers, got {size!r}")
+    return D, H, W
+
+
+def _label_values(label_values):
+    try:
+        vals = [int(v) for v in label_values]
+    except (TypeError, ValueError):
+        raise ValueError(f"label_values must be a sequence of integers, got {label_values!r}") from None
+    if len(vals) > MAX_LABEL_VALUES:
+        raise ValueError(f"at most {MAX_LABEL_VALUES} label values, got {len(vals)}")
+    if any(v == 0 for v in vals) or len(set(vals)) != len(vals):
+        raise ValueError("label_values must be distinct and non-zero (0 is always class 0)")
+    if any(not -2 ** 31 <= v < 2 ** 31 for v in vals):
+        raise ValueError("label_values must fit in int32")
+    return (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
+
+
+def _out_tensor(t, what, shape, dtype, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != device:
+        raise ValueError(f"out {what} must be a {dtype} tensor of shape {shape} on {device}")
+    if not t.is_contiguous():
+        raise ValueError(f"out {what} must be contiguous")
+    return t
+
+
+def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, out=None):
+    """samples: sequence of (ct, mr, ct_label | None), every array an own-shaped (d, h, w) CUDA tensor (images int16 / float32,
+    labels int16 / int32), labels present for all samples or for none.  out: optional preallocated (image, label_map,
+    crop_indexes) to write into.  -> (image fp16 [B, 2, D, H, W], label_map uint8 [B, D, H, W] | None, crop_indexes int32 [B, 3, 2])."""
+    D, H, W = _size(size)
+    vals, nvals = _label_values(label_values)
+    samples = list(samples)
+    if not samples:
+        raise ValueError("load_batch needs at least one sample")
+    B = len(samples)
+    items = (LoaderSample * B)()
+    device, has_label = None, None
+    for b, smp in enumerate(samples):
+        if not isinstance(smp, (tuple, list)) or len(smp) != 3:
+            raise ValueError(f"sample {b} must be a (ct, mr, ct_label | None) triple")
+        ct, mr, lab = smp
+        _typed(ct, f"sample {b}: ct", _IMAGE_DTYPES)                 # (types of the whole triple first: TypeError before ValueError)
+        _typed(mr, f"sample {b}: mr", _IMAGE_DTYPES)
+        if lab is not None:
+            _typed(lab, f"sample {b}: ct_label", _LABEL_DTYPES)
+        it = items[b]
+        it.ct, shape, it.ct_dtype = _volume(ct, f"sample {b}: ct", _IMAGE_DTYPES, device)
+        it.ct_shape[:] = shape
+        device = ct.device
+        it.mr, shape, it.mr_dtype = _volume(mr, f"sample {b}: mr", _IMAGE_DTYPES, device)
+        it.mr_shape[:] = shape
+        if has_label is None:
+            has_label = lab is not None
+        elif has_label != (lab is not None):
+            raise ValueError("either every sample of a batch has a ct_label or none has")
+        if lab is not None:
+            it.label, shape, it.label_dtype = _volume(lab, f"sample {b}: ct_label", _LABEL_DTYPES, device)
+            it.label_shape[:] = shape
+    if out is None:
+        image = torch.empty((B, 2, D, H, W), dtype=torch.float16, device=device)
+        label_map = torch.empty((B, D, H, W), dtype=torch.uint8, device=device) if has_label else None
+        crop = torch.empty((B, 3, 2), dtype=torch.int32, device=device)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 3:
+            raise ValueError("out must be an (image, label_map | None, crop_indexes) triple")
+        image = _out_tensor(out[0], "image", (B, 2, D, H, W), torch.float16, device)
+        if has_label != (out[1] is not None):
+            raise ValueError("out label_map must be given exactly when the samples have labels")
+        label_map = _out_tensor(out[1], "label_map", (B, D, H, W), torch.uint8, device) if has_label else None
+        crop = _out_tensor(out[2], "crop_indexes", (B, 3, 2), torch.int32, device)
+    nbytes = int(lib.micf_volume_loader_workspace(B))
+    _check("micf_volume_loader_workspace", 0 if nbytes >= 0 else nbytes)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _check("micf_volume_loader",
+               lib.micf_volume_loader(ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals, ws.data_ptr(), nbytes,
+                                      image.data_ptr(), None if label_map is None else label_map.data_ptr(), crop.data_ptr(),
+                                      _lib.stream()))
+    return image, label_map, crop
+
+
+def load_pair(ct, mr, ct_label=None, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES):
+    """One sample: -> (image fp16 [2, D, H, W], label_map uint8 [D, H, W] | None, crop_indexes int32 [3, 2])."""
+    image, label_map, crop = load_batch([(ct, mr, ct_label)], size=size, label_values=label_values)
+    return image[0], None if label_map is None else label_map[0], crop[0]
+
+
+__all__ = ["load_pair", "load_batch", "MMWHS_LABEL_VALUES", "SIGNATURES"]

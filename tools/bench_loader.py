@@ -1,0 +1,94 @@
+"""Time micformer_amd.loader.load_batch on a full-size MM-WHS-like pair (363x512x512 int16 CT + float32 MR + int16 CT label -> 128^3);
+one JSON line per batch size.
+
+    python tools/bench_loader.py [--batches 1,4] [--min-seconds 0.5] [--no-cpu]
+
+ms_per_call: device events around >= min-seconds of calls after warm-up (the whole call: workspace zeroing, min/max, resize + label + crop,
+crop finish).  minmax_ms: the same call with a 1x1x1 target, i.e. the full read of the raw image volumes plus launch overheads;
+minmax_GBps: the raw image bytes of the batch (the bytes that pass must read) over that time.  resize_ms: the difference of the two.
+Per-kernel times proper come from a kernel trace of this script (loader_minmax_kernel / loader_resize_kernel / loader_crop_kernel).
+cpu_s: the CPU referee (tests/loader_ref.py: numpy + F.interpolate, the reference's own operators) for ONE sample on this host.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+SHAPE = (363, 512, 512)
+SIZE = (128, 128, 128)
+
+
+def make_sample(seed):
+    import loader_ref
+    g = np.random.default_rng(seed)
+    ct = g.integers(-1024, 3072, size=SHAPE, dtype=np.int16)
+    mr = g.random(SHAPE, dtype=np.float32) * np.float32(1200.0)
+    values = np.array((0,) + loader_ref.MMWHS_LABEL_VALUES, np.int16)
+    lab = values[g.integers(0, len(values), size=SHAPE)]
+    return ct, mr, lab
+
+
+def timed(fn, min_seconds):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    calls, ms = 0, 0.0
+    while ms < min_seconds * 1e3:
+        n = max(1, calls or 4)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        ms += e0.elapsed_time(e1)
+        calls += n
+    return ms / calls, calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,4")
+    ap.add_argument("--min-seconds", type=float, default=0.5)
+    ap.add_argument("--no-cpu", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_loader.py needs the GPU")
+    import loader_ref
+    from micformer_amd import loader
+    batches = [int(b) for b in a.batches.split(",")]
+    host = make_sample(0)
+    cpu = None
+    if not a.no_cpu:
+        t0 = time.perf_counter()
+        loader_ref.load_pair(*host, size=SIZE)
+        cpu = time.perf_counter() - t0
+    first = tuple(torch.from_numpy(x).cuda() for x in host)
+    samples = [first] + [tuple(t.clone() for t in first) for _ in range(max(batches) - 1)]      # distinct buffers per sample
+    raw_bytes = sum(t.numel() * t.element_size() for t in first[:2])
+    for B in batches:
+        dev = samples[:B]
+        out = (torch.empty((B, 2) + SIZE, dtype=torch.float16, device="cuda"),
+               torch.empty((B,) + SIZE, dtype=torch.uint8, device="cuda"), torch.empty((B, 3, 2), dtype=torch.int32, device="cuda"))
+        tiny = (torch.empty((B, 2, 1, 1, 1), dtype=torch.float16, device="cuda"),
+                torch.empty((B, 1, 1, 1), dtype=torch.uint8, device="cuda"), torch.empty((B, 3, 2), dtype=torch.int32, device="cuda"))
+        total, calls = timed(lambda: loader.load_batch(dev, size=SIZE, out=out), a.min_seconds)
+        mm, _ = timed(lambda: loader.load_batch(dev, size=(1, 1, 1), out=tiny), a.min_seconds)
+        print(json.dumps({"case": "x".join(map(str, SHAPE)) + " -> " + "x".join(map(str, SIZE)), "B": B,
+                          "ms_per_call": round(total, 4), "ms_per_pair": round(total / B, 4), "calls": calls,
+                          "minmax_ms": round(mm, 4), "minmax_GBps": round(B * raw_bytes / mm / 1e6, 1),
+                          "resize_ms": round(total - mm, 4), "raw_image_bytes_per_pair": raw_bytes,
+                          "cpu_s": None if cpu is None else round(cpu, 3),
+                          "crop_indexes": out[2][0].cpu().tolist()}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
