@@ -1,0 +1,183 @@
+"""Predictions back to the geometry of the scan they came from: the inverse of `micformer_amd.loader`.  [B, K, D, H, W] float32
+logits of the network grid -> per sample a label volume of its OWN shape (d, h, w) holding the dataset's label values, on the HIP
+kernels of csrc/volume_restore.hip: trilinear upsample (align_corners=False) of the K class planes + argmax over K + class ->
+label value in one fused pass.  The upsampled [K, d, h, w] tensor (3 GB at 8 x 363 x 512 x 512) is never written.
+
+    from micformer_amd import loader, restore
+    labels = restore.restore_labels(logits[0], ct.shape)                     # int16 (d, h, w): 0, 205, 420, ... 850
+    labels = restore.restore_batch(logits, [ct.shape for ct in cts])         # a list, every sample with its own shape
+    labels = restore.segment_pair(model, ct, mr)                             # raw CT / MR pair in, segmentation of the CT out
+
+What is computed, per output voxel:
+  * the coordinate rule of F.interpolate(mode="trilinear", align_corners=False) in float32, exactly (the rule the reference's loader
+    applies in the other direction, MMWHS.py:332); only the order of the eight-product sum is this library's own.
+  * probabilities=False interpolates the logits as they are; probabilities=True interpolates softmax(logits, 1), evaluated once per
+    voxel of the LOW-resolution grid by a pre-pass (the two give different labels on the order of 1 % of the voxels).
+  * argmax over K, the lowest class winning an exact tie; NaN logits are unspecified.
+  * class 0 -> 0, class k -> label_values[k - 1] (`len(label_values) == K - 1`), stored as `dtype` (int16 / int32);
+    label_values=None -> the uint8 class map itself.
+
+Nothing here synchronises with the host or runs an ATen compute op (allocation only); the launches go to the current stream and
+can be captured by torch.cuda.graph when `out` is given (with probabilities=True the capture then owns the softmax workspace, 64 MB
+at 8 x 128^3, in the graph's memory pool).  The entry points are declared in include/micformer_restore.h and bound
+from their own ctypes table (SIGNATURES below), apart from include/micformer_hip.h's.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+from .loader import MMWHS_LABEL_VALUES
+
+MAX_CLASSES = 32
+MAX_EXTENT = 2048
+OUT_U8, OUT_I16, OUT_I32 = 0, 1, 2
+LOGITS, PROBS = 0, 1
+_OUT_DTYPES = {torch.int16: OUT_I16, torch.int32: OUT_I32}
+
+# name -> argument signature (as _lib.SIGNATURES); the workspace query returns int64, the other int
+SIGNATURES = {
+    "micf_volume_restore_workspace": "iiiiii",
+    "micf_volume_restore": "piiiiipiipiplp",
+}
+_RESTYPE = {"micf_volume_restore_workspace": _lib._L}
+
+
+class RestoreSample(ctypes.Structure):
+    """struct micf_restore_sample (include/micformer_restore.h)."""
+    _fields_ = [("out", ctypes.c_void_p), ("out_shape", ctypes.c_int32 * 3)]
+
+
+def _bind():
+    lib = _lib.lib
+    for name, sig in SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise ImportError(f"{_lib.LIB_PATH} predates the volume restore ({name} is missing): rebuild it with "
+                              "`python -c \"import __graft_entry__ as g; g.build()\"`") from None
+        fn.argtypes = [_lib._T[c] for c in sig]
+        fn.restype = _RESTYPE.get(name, _lib._I)
+    return lib
+
+
+lib = _bind()
+
+
+def _check(name, rc):
+    if rc != 0:
+        raise _lib.MicfError(f"{name} failed: {_lib.lib.micf_strerror(rc).decode()} (code {rc})")
+
+
+def _shape(shape, what):
+    try:
+        d, h, w = (int(s) for s in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what} must be three integers in 1..{MAX_EXTENT}, got {shape!r}") from None
+    if min(d, h, w) < 1 or max(d, h, w) > MAX_EXTENT or d * h * w >= 2 ** 31:
+        raise ValueError(f"{what} must be three integers in 1..{MAX_EXTENT} with fewer than 2^31 voxels, got {shape!r}")
+    return d, h, w
+
+
+def _label_values(label_values, K, dtype):
+    try:
+        vals = [int(v) for v in label_values]
+    except (TypeError, ValueError):
+        raise ValueError(f"label_values must be a sequence of integers or None, got {label_values!r}") from None
+    if len(vals) != K - 1:
+        raise ValueError(f"{K} classes need {K - 1} label values (class 0 is always 0), got {len(vals)}")
+    info = torch.iinfo(dtype)
+    if any(not info.min <= v <= info.max for v in vals):
+        raise ValueError(f"label_values must fit in {dtype}")
+    return (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
+
+
+def restore_batch(logits, shapes, label_values=MMWHS_LABEL_VALUES, probabilities=False, dtype=torch.int16, out=None):
+    """logits: [B, K, D, H, W] float32 CUDA tensor, contiguous, 1 <= K <= 32.  shapes: one (d, h, w) per sample.  label_values: K - 1
+    integers, or None for the uint8 class map.  out: optional list of B preallocated (d, h, w) tensors to write into.
+    -> list of B label volumes (`dtype`, or uint8 with label_values=None)."""
+    if not isinstance(logits, torch.Tensor):
+        raise TypeError(f"logits must be a tensor, got {type(logits).__name__}")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"logits must be torch.float32, got {logits.dtype}")
+    if label_values is not None and dtype not in _OUT_DTYPES:
+        raise TypeError(f"dtype must be torch.int16 or torch.int32, got {dtype}")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or not all(isinstance(t, torch.Tensor) for t in out):
+            raise TypeError("out must be a list of tensors, one per sample")
+    out_dtype = torch.uint8 if label_values is None else dtype
+    # what does not depend on the device first (as loader.py checks `size` and `label_values`), then device and layout
+    if logits.dim() != 5 or min(logits.shape) < 1:
+        raise ValueError(f"logits must be a non-empty [B, K, D, H, W] tensor, got shape {tuple(logits.shape)}")
+    B, K, D, H, W = logits.shape
+    if K > MAX_CLASSES:
+        raise ValueError(f"at most {MAX_CLASSES} classes, got {K}")
+    if D * H * W > 512 ** 3:
+        raise ValueError(f"at most 512^3 source voxels, got {D}x{H}x{W}")
+    try:
+        shapes = list(shapes)
+    except TypeError:
+        raise ValueError(f"shapes must be a sequence of (d, h, w), one per sample, got {shapes!r}") from None
+    if len(shapes) != B:
+        raise ValueError(f"{B} samples need {B} output shapes, got {len(shapes)}")
+    shapes = [_shape(s, f"shape of sample {b}") for b, s in enumerate(shapes)]
+    if label_values is None:
+        vals, nvals = None, 0
+    else:
+        vals, nvals = _label_values(label_values, K, dtype)
+    if not logits.is_cuda:
+        raise ValueError("micformer_amd.restore runs on the GPU: logits must be a CUDA (ROCm) tensor")
+    if not logits.is_contiguous():
+        raise ValueError("logits must be contiguous")
+    device = logits.device
+    if out is None:
+        out = [torch.empty(s, dtype=out_dtype, device=device) for s in shapes]
+    else:
+        if len(out) != B:
+            raise ValueError(f"out must hold {B} tensors, got {len(out)}")
+        for b, (t, s) in enumerate(zip(out, shapes)):
+            if t.dtype != out_dtype or tuple(t.shape) != s or t.device != device:
+                raise ValueError(f"out[{b}] must be a {out_dtype} tensor of shape {s} on {device}")
+            if not t.is_contiguous():
+                raise ValueError(f"out[{b}] must be contiguous")
+        out = list(out)
+    items = (RestoreSample * B)()
+    for it, t, s in zip(items, out, shapes):
+        it.out = t.data_ptr()
+        it.out_shape[:] = s
+    interpoland = PROBS if probabilities else LOGITS
+    nbytes = int(lib.micf_volume_restore_workspace(B, K, D, H, W, interpoland))
+    _check("micf_volume_restore_workspace", 0 if nbytes >= 0 else nbytes)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+    with torch.cuda.device(device):
+        _check("micf_volume_restore",
+               lib.micf_volume_restore(logits.data_ptr(), B, K, D, H, W, ctypes.addressof(items),
+                                       OUT_U8 if label_values is None else _OUT_DTYPES[dtype], interpoland,
+                                       None if vals is None else ctypes.addressof(vals), nvals,
+                                       None if ws is None else ws.data_ptr(), nbytes, _lib.stream()))
+    return out
+
+
+def restore_labels(logits, shape, label_values=MMWHS_LABEL_VALUES, probabilities=False, dtype=torch.int16, out=None):
+    """One sample: logits [K, D, H, W] (or [1, K, D, H, W]) -> the (d, h, w) label volume."""
+    if isinstance(logits, torch.Tensor) and logits.dim() == 4:
+        logits = logits.unsqueeze(0)
+    elif isinstance(logits, torch.Tensor) and (logits.dim() != 5 or logits.shape[0] != 1):
+        raise ValueError(f"restore_labels takes one sample, [K, D, H, W] or [1, K, D, H, W], got shape {tuple(logits.shape)}")
+    return restore_batch(logits, [shape], label_values=label_values, probabilities=probabilities, dtype=dtype,
+                         out=None if out is None else [out])[0]
+
+
+def segment_pair(model, ct, mr, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, probabilities=False):
+    """Raw CT / MR volumes of one sample (own-shaped (d, h, w) CUDA tensors, int16 / float32) -> the label volume of the CT's own
+    shape: loader.load_pair -> data.prepare_raw_batch(image, None, None) (the validation transform) -> model under no_grad ->
+    restore_labels at ct.shape."""
+    from . import data, loader
+    image, _, _ = loader.load_pair(ct, mr, None, size=size)
+    x, _ = data.prepare_raw_batch(image.unsqueeze(0), None, None)
+    with torch.no_grad():
+        logits = model(x)
+    return restore_labels(logits.float().contiguous(), tuple(ct.shape), label_values=label_values, probabilities=probabilities)
+
+
+__all__ = ["restore_batch", "restore_labels", "segment_pair", "MMWHS_LABEL_VALUES", "SIGNATURES"]
