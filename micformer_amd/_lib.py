@@ -32,8 +32,8 @@ LIB_PATH = os.environ.get("MICF_LIB") or os.path.join(_HERE, "libmicformer_hip.s
 _P, _I, _L, _F, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 _T = {"p": _P, "i": _I, "l": _L, "f": _F, "d": _D}
 
-# name -> argument signature (p pointer, i int, l int64, f float, d double); every function returns int
-# except micf_strerror.  Mirrors include/micformer_hip.h one to one (tests/test_abi.py checks the header).
+# name -> argument signature (p pointer, i int, l int64, f float, d double); the functions return int, those of INT64_RETURNS
+# (below) int64_t.  Mirrors include/micformer_hip.h one to one (tests/test_abi.py checks the header and what bind() set).
 SIGNATURES = {
     "micf_layernorm_fwd": "ppippppplifp",
     "micf_layernorm_bwd": "pppippppppplippp",
@@ -218,33 +218,36 @@ class MicfError(RuntimeError):
     pass
 
 
+# the main table's entry points that return int64_t (a byte / element count); every other one returns int
+INT64_RETURNS = frozenset((
+    "micf_linear_bwd_weight_workspace", "micf_linear_bwd_weight_grouped_workspace", "micf_conv3_bwd_data_workspace",
+    "micf_offset_sample_bwd_workspace", "micf_conv3_bwd_weight_workspace", "micf_conv3_bwd_weight_grouped_workspace",
+    "micf_head_tail_pack_bytes", "micf_head_tail_loss_parts", "micf_head_tail_bwd_weight_fused_workspace",
+    "micf_conv3_fwd_workspace", "micf_offset_head_bwd_workspace"))
+
+
+def bind(signatures, int64=(), feature=None, library=None):
+    """Sets argtypes (from the signature string) and restype (int64_t for the names in `int64`, else int) of every entry point of
+    a table and returns the library.  `feature` names the front end the table belongs to in the error for a missing symbol."""
+    library = lib if library is None else library
+    for name, sig in signatures.items():
+        try:
+            fn = getattr(library, name)
+        except AttributeError:
+            what = f"predates the {feature} ({name} is missing)" if feature else f"does not export {name}"
+            raise ImportError(f"{LIB_PATH} {what}: rebuild it with "
+                              "`python -c \"import __graft_entry__ as g; g.build()\"`") from None
+        fn.argtypes = [_T[c] for c in sig]
+        fn.restype = _L if name in int64 else _I
+    return library
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
             f"{LIB_PATH} not found: build it with `python micformer_amd/build.py` (hipcc, gfx950). "
             "micformer_amd has no CPU / PyTorch fallback path.")
-    lib = ctypes.CDLL(LIB_PATH)
-    for name, sig in SIGNATURES.items():
-        fn = getattr(lib, name)          # AttributeError if the symbol is missing: fail loudly
-        fn.argtypes = [_T[c] for c in sig]
-        fn.restype = _I
-    lib.micf_linear_bwd_weight_workspace.restype = _L
-    lib.micf_linear_bwd_weight_grouped_workspace.restype = _L
-    lib.micf_conv3_bwd_data_workspace.restype = _L
-    lib.micf_offset_sample_bwd_workspace.restype = _L
-    lib.micf_conv3_bwd_weight_workspace.restype = _L
-    lib.micf_conv3_bwd_weight_grouped_workspace.restype = _L
-    lib.micf_head_tail_pack_bytes.restype = _L
-    lib.micf_head_tail_loss_parts.restype = _L
-    lib.micf_head_tail_loss_parts.argtypes = [_I] * 4
-    lib.micf_head_tail_bwd_weight_fused_workspace.restype = _L
-    lib.micf_conv3_fwd_workspace.restype = _L
-    lib.micf_offset_head_bwd_workspace.restype = _L
-    lib.micf_block_tile_tokens.argtypes = [_I] * 8          # (no stream argument: a pure shape query)
-    lib.micf_block_saves_bf16.argtypes = [_I] * 3
-    lib.micf_offset_head_finish_deferrable.argtypes = [_I] * 4
-    lib.micf_block_fuses_sampler.argtypes = [_I] * 2
-    lib.micf_block_recomputes_h.argtypes = [_I] * 2
+    lib = bind(SIGNATURES, INT64_RETURNS, library=ctypes.CDLL(LIB_PATH))
     lib.micf_strerror.argtypes = [_I]
     lib.micf_strerror.restype = ctypes.c_char_p
     lib.micf_set_option.argtypes = [ctypes.c_char_p, _I]
@@ -368,7 +371,32 @@ def call(name, *args, cost=None):
             if len(cost) > 3 and cost[3] is not None:
                 rec[3] += cost[3]
     if rc != 0:
-        raise MicfError(f"{name} failed: {lib.micf_strerror(rc).decode()} (code {rc})")
+        raise _error(name, rc)
+
+
+def _error(name, rc):
+    return MicfError(f"{name} failed: {lib.micf_strerror(rc).decode()} (code {rc})")
+
+
+def check(name, rc):
+    if rc != 0:
+        raise _error(name, rc)
+
+
+# The front ends off the training step (metrics, loader, restore, postprocess) call the library through the two helpers below:
+# they count nothing (LAUNCHES, PROFILE, BLOCK_DEPTH and UNIT belong to the step's launches, which go through call()).
+def query_bytes(name, *args):
+    """A workspace query: the byte count it returns; a negative value is the library's error code."""
+    n = int(getattr(lib, name)(*args))
+    if n < 0:
+        raise _error(name, n)
+    return n
+
+
+def call_on(device, name, *args):
+    """Launch one entry point on torch's current stream of `device`."""
+    with torch.cuda.device(device):
+        check(name, getattr(lib, name)(*args, stream()))
 
 
 def profile_start():

@@ -20,14 +20,14 @@ Two deliberate deviations from the reference: an int16 volume whose range exceed
 reference's int16 `image - min` wraps), and the label is a uint8 class map with 255 for "no plane set" instead of 8 bool planes.
 
 Nothing here synchronises with the host or runs an ATen compute op (allocation only); the launches go to the current stream and
-can be captured by torch.cuda.graph when `out` is given.  The entry points are declared in include/micformer_loader.h and bound
-from their own ctypes table (SIGNATURES below), apart from include/micformer_hip.h's.
+can be captured by torch.cuda.graph when `out` is given.  The entry points are declared in include/micformer_loader.h; _lib.bind binds
+them from this module's table (SIGNATURES below), which is apart from include/micformer_hip.h's.
 """
 import ctypes
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 
 MMWHS_LABEL_VALUES = (205, 420, 500, 550, 600, 820, 850)          # MMWHS.py:289; class k = label_values[k - 1], class 0 = label 0
 MAX_LABEL_VALUES = 254
@@ -35,12 +35,12 @@ DTYPE_I16, DTYPE_F32, DTYPE_I32 = 0, 1, 2
 _IMAGE_DTYPES = {torch.int16: DTYPE_I16, torch.float32: DTYPE_F32}
 _LABEL_DTYPES = {torch.int16: DTYPE_I16, torch.int32: DTYPE_I32}
 
-# name -> argument signature (as _lib.SIGNATURES); the workspace query returns int64, the other int
+# name -> argument signature (as _lib.SIGNATURES); the workspace query returns int64 (INT64_RETURNS), the other int
 SIGNATURES = {
     "micf_volume_loader_workspace": "i",
     "micf_volume_loader": "piiiipiplpppp",
 }
-_RESTYPE = {"micf_volume_loader_workspace": _lib._L}
+INT64_RETURNS = frozenset(("micf_volume_loader_workspace",))
 
 
 class LoaderSample(ctypes.Structure):
@@ -50,25 +50,7 @@ class LoaderSample(ctypes.Structure):
                 ("ct_dtype", ctypes.c_int32), ("mr_dtype", ctypes.c_int32), ("label_dtype", ctypes.c_int32)]
 
 
-def _bind():
-    lib = _lib.lib
-    for name, sig in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(f"{_lib.LIB_PATH} predates the volume loader ({name} is missing): rebuild it with "
-                              "`python -c \"import __graft_entry__ as g; g.build()\"`") from None
-        fn.argtypes = [_lib._T[c] for c in sig]
-        fn.restype = _RESTYPE.get(name, _lib._I)
-    return lib
-
-
-lib = _bind()
-
-
-def _check(name, rc):
-    if rc != 0:
-        raise _lib.MicfError(f"{name} failed: {_lib.lib.micf_strerror(rc).decode()} (code {rc})")
+lib = _lib.bind(SIGNATURES, INT64_RETURNS, feature="volume loader")
 
 
 def _typed(t, what, dtypes):
@@ -90,43 +72,20 @@ def _volume(t, what, dtypes, device):
     return t.data_ptr(), tuple(t.shape), dtypes[t.dtype]
 
 
-def _size(size):
-    try:
-        D, H, W = (int(s) for s in size)
-    except (TypeError, ValueError):
-        raise ValueError(f"size must be three positive integers, got {size!r}") from None
-    if min(D, H, W) < 1:
-        raise ValueError(f"size must be three positive integers, got {size!r}")
-    return D, H, W
-
-
 def _label_values(label_values):
-    try:
-        vals = [int(v) for v in label_values]
-    except (TypeError, ValueError):
-        raise ValueError(f"label_values must be a sequence of integers, got {label_values!r}") from None
+    vals = _args.ints(label_values)
     if len(vals) > MAX_LABEL_VALUES:
         raise ValueError(f"at most {MAX_LABEL_VALUES} label values, got {len(vals)}")
-    if any(v == 0 for v in vals) or len(set(vals)) != len(vals):
-        raise ValueError("label_values must be distinct and non-zero (0 is always class 0)")
-    if any(not -2 ** 31 <= v < 2 ** 31 for v in vals):
-        raise ValueError("label_values must fit in int32")
-    return (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
-
-
-def _out_tensor(t, what, shape, dtype, device):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or t.device != device:
-        raise ValueError(f"out {what} must be a {dtype} tensor of shape {shape} on {device}")
-    if not t.is_contiguous():
-        raise ValueError(f"out {what} must be contiguous")
-    return t
+    _args.distinct_nonzero(vals)
+    _args.fit(vals, torch.int32)
+    return _args.int32_array(vals), len(vals)
 
 
 def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, out=None):
     """samples: sequence of (ct, mr, ct_label | None), every array an own-shaped (d, h, w) CUDA tensor (images int16 / float32,
     labels int16 / int32), labels present for all samples or for none.  out: optional preallocated (image, label_map,
     crop_indexes) to write into.  -> (image fp16 [B, 2, D, H, W], label_map uint8 [B, D, H, W] | None, crop_indexes int32 [B, 3, 2])."""
-    D, H, W = _size(size)
+    D, H, W = _args.triple(size, "size")
     vals, nvals = _label_values(label_values)
     samples = list(samples)
     if not samples:
@@ -162,19 +121,15 @@ def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, o
     else:
         if not isinstance(out, (tuple, list)) or len(out) != 3:
             raise ValueError("out must be an (image, label_map | None, crop_indexes) triple")
-        image = _out_tensor(out[0], "image", (B, 2, D, H, W), torch.float16, device)
+        image = _args.out_tensor(out[0], "out image", (B, 2, D, H, W), torch.float16, device)
         if has_label != (out[1] is not None):
             raise ValueError("out label_map must be given exactly when the samples have labels")
-        label_map = _out_tensor(out[1], "label_map", (B, D, H, W), torch.uint8, device) if has_label else None
-        crop = _out_tensor(out[2], "crop_indexes", (B, 3, 2), torch.int32, device)
-    nbytes = int(lib.micf_volume_loader_workspace(B))
-    _check("micf_volume_loader_workspace", 0 if nbytes >= 0 else nbytes)
+        label_map = _args.out_tensor(out[1], "out label_map", (B, D, H, W), torch.uint8, device) if has_label else None
+        crop = _args.out_tensor(out[2], "out crop_indexes", (B, 3, 2), torch.int32, device)
+    nbytes = _lib.query_bytes("micf_volume_loader_workspace", B)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        _check("micf_volume_loader",
-               lib.micf_volume_loader(ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals, ws.data_ptr(), nbytes,
-                                      image.data_ptr(), None if label_map is None else label_map.data_ptr(), crop.data_ptr(),
-                                      _lib.stream()))
+    _lib.call_on(device, "micf_volume_loader", ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals, ws.data_ptr(),
+                 nbytes, image.data_ptr(), None if label_map is None else label_map.data_ptr(), crop.data_ptr())
     return image, label_map, crop
 
 

@@ -6,8 +6,8 @@ from MONAI 1.1 (monai.metrics.HausdorffDistanceMetric / MeanIoU) on the HIP kern
 
 Inputs are either uint8 class maps [B, D, H, W] (num_classes required) or one-hot planes [B, K, D, H, W] of any dtype (cast
 with .float() as MONAI does; a voxel is in class c where the plane equals 1.0).  Nothing here synchronises with the host.
-The entry points are declared in include/micformer_metrics.h and bound from their own ctypes table (SIGNATURES below), apart
-from include/micformer_hip.h's.
+The entry points are declared in include/micformer_metrics.h; _lib.bind binds them from this module's table (SIGNATURES below),
+which is apart from include/micformer_hip.h's.
 """
 import torch
 
@@ -15,35 +15,16 @@ from . import _lib
 
 FORM_LABEL, FORM_ONEHOT = 0, 1
 
-# name -> argument signature (as _lib.SIGNATURES); the two *_workspace queries return int64, the others int
+# name -> argument signature (as _lib.SIGNATURES); the two *_workspace queries return int64 (INT64_RETURNS), the others int
 SIGNATURES = {
     "micf_surface_metrics_workspace": "iiiii",
     "micf_hausdorff_distance": "ppiiiiiiidiplpp",
     "micf_mean_iou_workspace": "iiiii",
     "micf_mean_iou": "ppiiiiiiiiplpp",
 }
-_RESTYPE = {"micf_surface_metrics_workspace": _lib._L, "micf_mean_iou_workspace": _lib._L}
+INT64_RETURNS = frozenset(("micf_surface_metrics_workspace", "micf_mean_iou_workspace"))
 
-
-def _bind():
-    lib = _lib.lib
-    for name, sig in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(f"{_lib.LIB_PATH} predates the surface metrics ({name} is missing): rebuild it with "
-                              "`python -c \"import __graft_entry__ as g; g.build()\"`") from None
-        fn.argtypes = [_lib._T[c] for c in sig]
-        fn.restype = _RESTYPE.get(name, _lib._I)
-    return lib
-
-
-lib = _bind()
-
-
-def _check(name, rc):
-    if rc != 0:
-        raise _lib.MicfError(f"{name} failed: {_lib.lib.micf_strerror(rc).decode()} (code {rc})")
+lib = _lib.bind(SIGNATURES, INT64_RETURNS, feature="surface metrics")
 
 
 def _inputs(y_pred, y, num_classes):
@@ -88,14 +69,11 @@ def hausdorff_distance(y_pred, y, num_classes=None, include_background=False, pe
         raise ValueError(f"percentile should be a value between 0 and 100, got {percentile}")
     pred, gt, form, B, K, D, H, W = _inputs(y_pred, y, num_classes)
     first = _first_class(include_background, K)
-    nbytes = lib.micf_surface_metrics_workspace(B, K, D, H, W)
-    _check("micf_surface_metrics_workspace", 0 if nbytes >= 0 else int(nbytes))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=pred.device)
+    nbytes = _lib.query_bytes("micf_surface_metrics_workspace", B, K, D, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     out = torch.empty((B, K - first), dtype=torch.float32, device=pred.device)
-    with torch.cuda.device(pred.device):
-        _check("micf_hausdorff_distance",
-               lib.micf_hausdorff_distance(pred.data_ptr(), gt.data_ptr(), form, B, K, D, H, W, first, p, 1 if directed else 0,
-                                           ws.data_ptr(), int(nbytes), out.data_ptr(), _lib.stream()))
+    _lib.call_on(pred.device, "micf_hausdorff_distance", pred.data_ptr(), gt.data_ptr(), form, B, K, D, H, W, first, p,
+                 1 if directed else 0, ws.data_ptr(), nbytes, out.data_ptr())
     return out
 
 
@@ -103,13 +81,11 @@ def mean_iou(y_pred, y, num_classes=None, include_background=False, ignore_empty
     """MONAI 1.1 compute_iou on the device: float32 [B, K'] from exact integer counts."""
     pred, gt, form, B, K, D, H, W = _inputs(y_pred, y, num_classes)
     first = _first_class(include_background, K)
-    nbytes = lib.micf_mean_iou_workspace(B, K, D, H, W)
-    _check("micf_mean_iou_workspace", 0 if nbytes >= 0 else int(nbytes))
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=pred.device)
+    nbytes = _lib.query_bytes("micf_mean_iou_workspace", B, K, D, H, W)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
     out = torch.empty((B, K - first), dtype=torch.float32, device=pred.device)
-    with torch.cuda.device(pred.device):
-        _check("micf_mean_iou", lib.micf_mean_iou(pred.data_ptr(), gt.data_ptr(), form, B, K, D, H, W, first, 1 if ignore_empty else 0,
-                                                  ws.data_ptr(), int(nbytes), out.data_ptr(), _lib.stream()))
+    _lib.call_on(pred.device, "micf_mean_iou", pred.data_ptr(), gt.data_ptr(), form, B, K, D, H, W, first, 1 if ignore_empty else 0,
+                 ws.data_ptr(), nbytes, out.data_ptr())
     return out
 
 

@@ -24,29 +24,28 @@ Every result is an integer and bit-identical from run to run (integer atomics on
 
 Nothing here synchronises with the host or runs an ATen compute op (allocation only); the launches go to the current stream and
 can be captured by torch.cuda.graph when `out` is given (the capture then owns the workspace, 8 bytes per voxel).  The entry
-points are declared in include/micformer_components.h and bound from their own ctypes table (SIGNATURES below).
+points are declared in include/micformer_components.h; _lib.bind binds them from this module's table (SIGNATURES below).
 """
 import ctypes
 
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import MAX_CLASSES, MAX_EXTENT
 from .loader import MMWHS_LABEL_VALUES
 
-MAX_CLASSES = 32
-MAX_EXTENT = 2048
 MAX_VOXELS = 2 ** 31 - 1          # exclusive
 IN_U8, IN_I16, IN_I32 = 0, 1, 2
 KEEP_LARGEST, REMOVE_SMALL = 0, 1
 _IN_DTYPES = {torch.uint8: IN_U8, torch.int16: IN_I16, torch.int32: IN_I32}
 
-# name -> argument signature (as _lib.SIGNATURES); the workspace query returns int64, the others int
+# name -> argument signature (as _lib.SIGNATURES); the workspace query returns int64 (INT64_RETURNS), the others int
 SIGNATURES = {
     "micf_components_workspace": "pi",
     "micf_connected_components": "piiipiipplp",
     "micf_filter_components": "piiipiiliiplp",
 }
-_RESTYPE = {"micf_components_workspace": _lib._L}
+INT64_RETURNS = frozenset(("micf_components_workspace",))
 
 
 class ComponentSample(ctypes.Structure):
@@ -54,25 +53,7 @@ class ComponentSample(ctypes.Structure):
     _fields_ = [("in_", ctypes.c_void_p), ("out", ctypes.c_void_p), ("shape", ctypes.c_int32 * 3)]
 
 
-def _bind():
-    lib = _lib.lib
-    for name, sig in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(f"{_lib.LIB_PATH} predates the connected components ({name} is missing): rebuild it with "
-                              "`python -c \"import __graft_entry__ as g; g.build()\"`") from None
-        fn.argtypes = [_lib._T[c] for c in sig]
-        fn.restype = _RESTYPE.get(name, _lib._I)
-    return lib
-
-
-lib = _bind()
-
-
-def _check(name, rc):
-    if rc != 0:
-        raise _lib.MicfError(f"{name} failed: {_lib.lib.micf_strerror(rc).decode()} (code {rc})")
+lib = _lib.bind(SIGNATURES, INT64_RETURNS, feature="connected components")
 
 
 def _volumes(volume, what="volume"):
@@ -114,10 +95,7 @@ def _classes_of(dtype, num_classes, label_values):
     else:
         if label_values is None:
             raise ValueError(f"an {dtype} label volume needs label_values (the value of every class but 0)")
-        try:
-            vals = [int(v) for v in label_values]
-        except (TypeError, ValueError):
-            raise ValueError(f"label_values must be a sequence of integers, got {label_values!r}") from None
+        vals = _args.ints(label_values)
         K = len(vals) + 1 if num_classes is None else num_classes
     if isinstance(K, bool) or not isinstance(K, int) or not 2 <= K <= MAX_CLASSES:
         raise ValueError(f"num_classes must be an integer in 2..{MAX_CLASSES}, got {K!r}")
@@ -125,12 +103,9 @@ def _classes_of(dtype, num_classes, label_values):
         return K, None, 0
     if len(vals) != K - 1:
         raise ValueError(f"{K} classes need {K - 1} label values (class 0 is always 0), got {len(vals)}")
-    info = torch.iinfo(dtype)
-    if any(not info.min <= v <= info.max for v in vals):
-        raise ValueError(f"label_values must fit in {dtype}")
-    if 0 in vals or len(set(vals)) != len(vals):
-        raise ValueError(f"label_values must be distinct and non-zero, got {tuple(vals)}")
-    return K, (ctypes.c_int32 * len(vals))(*vals), len(vals)
+    _args.fit(vals, dtype)
+    _args.distinct_nonzero(vals)
+    return K, _args.int32_array(vals), len(vals)
 
 
 def _connectivity(connectivity):
@@ -186,10 +161,7 @@ def _outputs(out, vols, pack, dtype, what="out"):
     else:
         raise TypeError(f"{what} must be a tensor or a list of tensors")
     for b, (o, t) in enumerate(zip(outs, vols)):
-        if o.dtype != dtype or tuple(o.shape) != tuple(t.shape) or o.device != device:
-            raise ValueError(f"{what}[{b}] must be a {dtype} tensor of shape {tuple(t.shape)} on {device}")
-        if not o.is_contiguous():
-            raise ValueError(f"{what}[{b}] must be contiguous")
+        _args.out_tensor(o, f"{what}[{b}]", t.shape, dtype, device)
     return outs, ret
 
 
@@ -207,14 +179,11 @@ def workspace_bytes(shapes):
     items = (ComponentSample * max(len(shapes), 1))()
     for it, s in zip(items, shapes):
         it.shape[:] = tuple(int(v) for v in s)
-    n = int(lib.micf_components_workspace(ctypes.addressof(items), len(shapes)))
-    _check("micf_components_workspace", 0 if n >= 0 else n)
-    return n
+    return _lib.query_bytes("micf_components_workspace", ctypes.addressof(items), len(shapes))
 
 
 def _workspace(items, B, device, workspace):
-    nbytes = int(lib.micf_components_workspace(ctypes.addressof(items), B))
-    _check("micf_components_workspace", 0 if nbytes >= 0 else nbytes)
+    nbytes = _lib.query_bytes("micf_components_workspace", ctypes.addressof(items), B)
     if workspace is None:
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
     elif workspace.dtype != torch.uint8 or workspace.device != device or workspace.numel() < nbytes or not workspace.is_contiguous():
@@ -238,12 +207,9 @@ def connected_components(volume, num_classes=None, label_values=MMWHS_LABEL_VALU
     device = vols[0].device
     ws, nbytes = _workspace(items, B, device, workspace)
     size_ptrs = (ctypes.c_void_p * B)(*[t.data_ptr() for t in sizes]) if return_sizes else None
-    with torch.cuda.device(device):
-        _check("micf_connected_components",
-               lib.micf_connected_components(ctypes.addressof(items), B, _IN_DTYPES[vols[0].dtype], K,
-                                             None if vals is None else ctypes.addressof(vals), nvals, conn,
-                                             None if size_ptrs is None else ctypes.addressof(size_ptrs), ws.data_ptr(), nbytes,
-                                             _lib.stream()))
+    _lib.call_on(device, "micf_connected_components", ctypes.addressof(items), B, _IN_DTYPES[vols[0].dtype], K,
+                 None if vals is None else ctypes.addressof(vals), nvals, conn,
+                 None if size_ptrs is None else ctypes.addressof(size_ptrs), ws.data_ptr(), nbytes)
     return (ret_l, ret_s) if return_sizes else ret_l
 
 
@@ -260,11 +226,8 @@ def _filter(volume, mode, min_size, num_classes, label_values, connectivity, cla
     B = len(vols)
     device = vols[0].device
     ws, nbytes = _workspace(items, B, device, workspace)
-    with torch.cuda.device(device):
-        _check("micf_filter_components",
-               lib.micf_filter_components(ctypes.addressof(items), B, _IN_DTYPES[vols[0].dtype], K,
-                                          None if vals is None else ctypes.addressof(vals), nvals, conn, mask, mode, min_size,
-                                          ws.data_ptr(), nbytes, _lib.stream()))
+    _lib.call_on(device, "micf_filter_components", ctypes.addressof(items), B, _IN_DTYPES[vols[0].dtype], K,
+                 None if vals is None else ctypes.addressof(vals), nvals, conn, mask, mode, min_size, ws.data_ptr(), nbytes)
     return ret
 
 

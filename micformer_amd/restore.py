@@ -19,28 +19,27 @@ What is computed, per output voxel:
 
 Nothing here synchronises with the host or runs an ATen compute op (allocation only); the launches go to the current stream and
 can be captured by torch.cuda.graph when `out` is given (with probabilities=True the capture then owns the softmax workspace, 64 MB
-at 8 x 128^3, in the graph's memory pool).  The entry points are declared in include/micformer_restore.h and bound
-from their own ctypes table (SIGNATURES below), apart from include/micformer_hip.h's.
+at 8 x 128^3, in the graph's memory pool).  The entry points are declared in include/micformer_restore.h; _lib.bind
+binds them from this module's table (SIGNATURES below), which is apart from include/micformer_hip.h's.
 """
 import ctypes
 
 import torch
 
-from . import _lib
+from . import _args, _lib
+from ._args import MAX_CLASSES, MAX_EXTENT
 from .loader import MMWHS_LABEL_VALUES
 
-MAX_CLASSES = 32
-MAX_EXTENT = 2048
 OUT_U8, OUT_I16, OUT_I32 = 0, 1, 2
 LOGITS, PROBS = 0, 1
 _OUT_DTYPES = {torch.int16: OUT_I16, torch.int32: OUT_I32}
 
-# name -> argument signature (as _lib.SIGNATURES); the workspace query returns int64, the other int
+# name -> argument signature (as _lib.SIGNATURES); the workspace query returns int64 (INT64_RETURNS), the other int
 SIGNATURES = {
     "micf_volume_restore_workspace": "iiiiii",
     "micf_volume_restore": "piiiiipiipiplp",
 }
-_RESTYPE = {"micf_volume_restore_workspace": _lib._L}
+INT64_RETURNS = frozenset(("micf_volume_restore_workspace",))
 
 
 class RestoreSample(ctypes.Structure):
@@ -48,48 +47,15 @@ class RestoreSample(ctypes.Structure):
     _fields_ = [("out", ctypes.c_void_p), ("out_shape", ctypes.c_int32 * 3)]
 
 
-def _bind():
-    lib = _lib.lib
-    for name, sig in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
-            raise ImportError(f"{_lib.LIB_PATH} predates the volume restore ({name} is missing): rebuild it with "
-                              "`python -c \"import __graft_entry__ as g; g.build()\"`") from None
-        fn.argtypes = [_lib._T[c] for c in sig]
-        fn.restype = _RESTYPE.get(name, _lib._I)
-    return lib
-
-
-lib = _bind()
-
-
-def _check(name, rc):
-    if rc != 0:
-        raise _lib.MicfError(f"{name} failed: {_lib.lib.micf_strerror(rc).decode()} (code {rc})")
-
-
-def _shape(shape, what):
-    try:
-        d, h, w = (int(s) for s in shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"{what} must be three integers in 1..{MAX_EXTENT}, got {shape!r}") from None
-    if min(d, h, w) < 1 or max(d, h, w) > MAX_EXTENT or d * h * w >= 2 ** 31:
-        raise ValueError(f"{what} must be three integers in 1..{MAX_EXTENT} with fewer than 2^31 voxels, got {shape!r}")
-    return d, h, w
+lib = _lib.bind(SIGNATURES, INT64_RETURNS, feature="volume restore")
 
 
 def _label_values(label_values, K, dtype):
-    try:
-        vals = [int(v) for v in label_values]
-    except (TypeError, ValueError):
-        raise ValueError(f"label_values must be a sequence of integers or None, got {label_values!r}") from None
+    vals = _args.ints(label_values)
     if len(vals) != K - 1:
         raise ValueError(f"{K} classes need {K - 1} label values (class 0 is always 0), got {len(vals)}")
-    info = torch.iinfo(dtype)
-    if any(not info.min <= v <= info.max for v in vals):
-        raise ValueError(f"label_values must fit in {dtype}")
-    return (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
+    _args.fit(vals, dtype)
+    return _args.int32_array(vals), len(vals)
 
 
 def restore_batch(logits, shapes, label_values=MMWHS_LABEL_VALUES, probabilities=False, dtype=torch.int16, out=None):
@@ -120,7 +86,7 @@ def restore_batch(logits, shapes, label_values=MMWHS_LABEL_VALUES, probabilities
         raise ValueError(f"shapes must be a sequence of (d, h, w), one per sample, got {shapes!r}") from None
     if len(shapes) != B:
         raise ValueError(f"{B} samples need {B} output shapes, got {len(shapes)}")
-    shapes = [_shape(s, f"shape of sample {b}") for b, s in enumerate(shapes)]
+    shapes = [_args.triple(s, f"shape of sample {b}", MAX_EXTENT, 2 ** 31) for b, s in enumerate(shapes)]
     if label_values is None:
         vals, nvals = None, 0
     else:
@@ -135,26 +101,17 @@ def restore_batch(logits, shapes, label_values=MMWHS_LABEL_VALUES, probabilities
     else:
         if len(out) != B:
             raise ValueError(f"out must hold {B} tensors, got {len(out)}")
-        for b, (t, s) in enumerate(zip(out, shapes)):
-            if t.dtype != out_dtype or tuple(t.shape) != s or t.device != device:
-                raise ValueError(f"out[{b}] must be a {out_dtype} tensor of shape {s} on {device}")
-            if not t.is_contiguous():
-                raise ValueError(f"out[{b}] must be contiguous")
-        out = list(out)
+        out = [_args.out_tensor(t, f"out[{b}]", s, out_dtype, device) for b, (t, s) in enumerate(zip(out, shapes))]
     items = (RestoreSample * B)()
     for it, t, s in zip(items, out, shapes):
         it.out = t.data_ptr()
         it.out_shape[:] = s
     interpoland = PROBS if probabilities else LOGITS
-    nbytes = int(lib.micf_volume_restore_workspace(B, K, D, H, W, interpoland))
-    _check("micf_volume_restore_workspace", 0 if nbytes >= 0 else nbytes)
+    nbytes = _lib.query_bytes("micf_volume_restore_workspace", B, K, D, H, W, interpoland)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
-    with torch.cuda.device(device):
-        _check("micf_volume_restore",
-               lib.micf_volume_restore(logits.data_ptr(), B, K, D, H, W, ctypes.addressof(items),
-                                       OUT_U8 if label_values is None else _OUT_DTYPES[dtype], interpoland,
-                                       None if vals is None else ctypes.addressof(vals), nvals,
-                                       None if ws is None else ws.data_ptr(), nbytes, _lib.stream()))
+    _lib.call_on(device, "micf_volume_restore", logits.data_ptr(), B, K, D, H, W, ctypes.addressof(items),
+                 OUT_U8 if label_values is None else _OUT_DTYPES[dtype], interpoland,
+                 None if vals is None else ctypes.addressof(vals), nvals, None if ws is None else ws.data_ptr(), nbytes)
     return out
 
 

@@ -1,42 +1,30 @@
-"""CPU-side checks of the C-ABI boundary: the library loads, exports every symbol include/micformer_hip.h declares,
-and the ctypes signatures in micformer_amd/_lib.py match the header argument by argument (no compute calls)."""
+"""CPU-side checks of the C-ABI boundary: the library loads, exports every symbol the five headers of include/ declare, and the
+ctypes tables of micformer_amd (_lib.py and the four front ends) match their header argument by argument (no compute calls)."""
 import ctypes
+import importlib
+import itertools
 import os
-import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "micformer_hip.h")
+import pytest
+
+import abi_header
+
+HEADER = "micformer_hip.h"
+# (header, the module of micformer_amd that holds its table, entry points in the table)
+TABLES = [("micformer_hip.h", "_lib", 97), ("micformer_metrics.h", "metrics", 4), ("micformer_loader.h", "loader", 2),
+          ("micformer_restore.h", "restore", 2), ("micformer_components.h", "postprocess", 3)]
 
 
-def parse_header():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(int64_t|int|const char\*)\s+(micf_\w+)\s*\(([^)]*)\)\s*;", src):
-        ret, name, args = m.group(1), m.group(2), m.group(3)
-        sig = ""
-        for a in [a.strip() for a in args.split(",") if a.strip() and a.strip() != "void"]:
-            if "*" in a or a.startswith("micf_stream_t"):
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("float "):
-                sig += "f"
-            elif a.startswith("double "):
-                sig += "d"
-            else:
-                raise AssertionError(f"unparsed argument {a!r} in {name}")
-        decls[name] = sig
-    return decls
+def main_signatures():
+    """The main header: name -> argument signature."""
+    return {name: sig for name, (_, sig) in abi_header.parse_header(HEADER).items()}
 
 
 _UNTABLED = ("micf_abi_version", "micf_strerror", "micf_set_option", "micf_get_option")     # bound by hand in _lib._load
 
 
 def test_header_declares_expected_entry_points():
-    d = parse_header()
+    d = main_signatures()
     assert len(d) == 101, sorted(d)         # (97 product entry points + micf_set_option / micf_get_option (test hooks) + the round-5 measurement probe + the MFMA hazard probe)
     assert all(sig.endswith("p") for n, sig in d.items()
                if n not in ("micf_abi_version", "micf_strerror", "micf_set_option", "micf_get_option", "micf_linear_bwd_weight_workspace",
@@ -52,7 +40,7 @@ def test_library_exports_every_declared_symbol():
     from micformer_amd.build import LIB
     assert os.path.exists(LIB), "run __graft_entry__.build() first"
     lib = ctypes.CDLL(LIB)
-    for name in parse_header():
+    for name in main_signatures():
         assert hasattr(lib, name), f"{name} declared in include/micformer_hip.h but not exported"
     assert lib.micf_abi_version() == 1
     lib.micf_strerror.restype = ctypes.c_char_p
@@ -61,7 +49,7 @@ def test_library_exports_every_declared_symbol():
 
 def test_ctypes_signatures_match_header():
     from micformer_amd import _lib
-    d = parse_header()
+    d = main_signatures()
     for name, sig in d.items():
         if name in _UNTABLED:
             continue
@@ -70,10 +58,44 @@ def test_ctypes_signatures_match_header():
     assert set(_lib.SIGNATURES) == set(d) - set(_UNTABLED)
 
 
+@pytest.mark.parametrize("header,module,count", TABLES, ids=[t[1] for t in TABLES])
+def test_header_table_binding_and_library_agree(header, module, count):
+    """Per header: the module's SIGNATURES names what the header declares, signature by signature; an int64_t return is in the
+    module's INT64_RETURNS; what _lib.bind set on the function objects (argtypes, restype) is what the header says; the built
+    library exports every symbol."""
+    from micformer_amd import _lib
+    mod = importlib.import_module(f"micformer_amd.{module}")
+    d = {n: v for n, v in abi_header.parse_header(header).items() if n not in _UNTABLED}
+    assert set(d) == set(mod.SIGNATURES) and len(d) == count
+    assert mod.lib is _lib.lib
+    exported = ctypes.CDLL(_lib.LIB_PATH)
+    for name, (ret, sig) in d.items():
+        assert mod.SIGNATURES[name] == sig, f"{name}: header {sig} vs ctypes {mod.SIGNATURES[name]}"
+        assert ret in ("int", "int64_t") and (name in mod.INT64_RETURNS) == (ret == "int64_t"), name
+        fn = getattr(_lib.lib, name)
+        assert list(fn.argtypes) == [abi_header.CTYPES[c] for c in sig], name
+        assert fn.restype is abi_header.RETURNS[ret], name
+        assert hasattr(exported, name), f"{name} declared but not exported"
+    assert set(mod.INT64_RETURNS) <= set(d)
+
+
+def test_tables_are_pairwise_disjoint():
+    tables = {module: set(importlib.import_module(f"micformer_amd.{module}").SIGNATURES) for _, module, _ in TABLES}
+    for a, b in itertools.combinations(tables, 2):
+        assert not tables[a] & tables[b], (a, b)
+
+
+def test_missing_symbol_is_an_import_error_that_names_it():
+    from micformer_amd import _lib
+    with pytest.raises(ImportError, match=r"predates the patch sampler \(micf_no_such_entry is missing\).*g\.build\(\)"):
+        _lib.bind({"micf_no_such_entry": "ip"}, feature="patch sampler")
+    with pytest.raises(ImportError, match=r"does not export micf_no_such_entry.*g\.build\(\)"):
+        _lib.bind({"micf_no_such_entry": "ip"})
+
+
 def test_option_hooks_round_trip_and_reject_unknown_names():
     """micf_set_option / micf_get_option: every documented hook reads back what was set and is restored; an unknown name is an error
     (no silent no-op for a mistyped hook)."""
-    import pytest
     from micformer_amd import _lib
     defaults = {"block_wave": 1, "block_recompute_h": 0, "block_debug": 0, "sample_tile": 1, "sample_e": -1, "cell_cap": -1,
                 "tile_cap_hits": -1, "tile_cap_cell": -1, "tile_cap_voxel": -1}
@@ -129,27 +151,9 @@ def test_round2_entry_points_validate_arguments_without_gpu():
     assert L.micf_adam_step(None, None, None, None, 8, None, C.c_float(0.9), C.c_float(0.999), C.c_float(1e-8), C.c_float(1.0), None, None) == EINVAL
 
 
-def _struct_fields(header_text, name):
-    """Pointer field names of `typedef struct NAME { ... } NAME;` in declaration order (comments stripped)."""
-    import re
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), header_text, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        # "const float *a, *b" / "float* y" / "const void *wq, *wkv" / "void* h"
-        first, *rest = decl.split(",")
-        names.append(first.replace("*", " ").split()[-1])
-        names.extend(r.replace("*", " ").split()[-1] for r in rest)
-    return names
-
-
 def test_block_group_structs_mirror_the_header_field_by_field():
     """The ctypes mirrors of micf_block_fwd_group / micf_block_bwd_group (arrays of them are what micf_block_fwd / _bwd receive)
     list the header's fields in the header's order: a field added on one side only shifts every pointer behind it."""
     from micformer_amd import _lib
-    text = open(HEADER).read()
-    assert tuple(_struct_fields(text, "micf_block_fwd_group")) == _lib.BlockFwdGroup.FIELDS
-    assert tuple(_struct_fields(text, "micf_block_bwd_group")) == _lib.BlockBwdGroup.FIELDS
+    assert tuple(abi_header.struct_fields(HEADER, "micf_block_fwd_group")) == _lib.BlockFwdGroup.FIELDS
+    assert tuple(abi_header.struct_fields(HEADER, "micf_block_bwd_group")) == _lib.BlockBwdGroup.FIELDS

@@ -1,18 +1,16 @@
-"""CPU checks of the connected components: the referee (tests/components_ref.py) against a flood fill, the C-ABI of
-include/micformer_components.h against the ctypes table and the library, argument errors caught before any launch, the workspace
+"""CPU checks of the connected components: the referee (tests/components_ref.py) against a flood fill, the ctypes struct and constants against
+include/micformer_components.h (tests/test_abi.py has the entry points), argument errors caught before any launch, the workspace
 query, and the Python front end's validation."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import components_ref as C
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "micformer_components.h")
+HEADER = "micformer_components.h"
 EINVAL, EUNSUP = -1, -2
 
 
@@ -63,46 +61,12 @@ def test_referee_filters_and_scenes():
 
 # ---- the C-ABI --------------------------------------------------------------------------------------------------------------
 
-def parse_header():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(int64_t|int)\s+(micf_\w+)\s*\(([^)]*)\)\s*;", src):
-        sig = ""
-        for a in [a.strip() for a in m.group(3).split(",") if a.strip()]:
-            if "*" in a or a.startswith("micf_stream_t"):
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            else:
-                raise AssertionError(f"unparsed argument {a!r} in {m.group(2)}")
-        decls[m.group(2)] = (m.group(1), sig)
-    return decls
-
-
-def test_components_header_matches_ctypes_table_and_library():
-    from micformer_amd import _lib, loader, metrics, postprocess, restore
-    d = parse_header()
-    assert set(d) == set(postprocess.SIGNATURES) and len(d) == 3
-    for name, (ret, sig) in d.items():
-        assert postprocess.SIGNATURES[name] == sig, name
-        assert (postprocess._RESTYPE.get(name) is _lib._L) == (ret == "int64_t"), name
-        for other in (_lib, metrics, loader, restore):
-            assert name not in other.SIGNATURES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in d:
-        assert hasattr(lib, name), f"{name} declared but not exported"
-
-
 def test_sample_struct_and_constants_match_the_header():
     from micformer_amd import postprocess as P
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef struct micf_component_sample \{(.*?)\} micf_component_sample;", src, flags=re.S).group(1)
-    assert [d.strip() for d in body.split(";") if d.strip()] == ["const void* in", "void* out", "int32_t shape[3]"]
+    assert abi_header.struct_decls(HEADER, "micf_component_sample") == ["const void* in", "void* out", "int32_t shape[3]"]
     assert [t for _, t in P.ComponentSample._fields_] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32 * 3]
     assert ctypes.sizeof(P.ComponentSample) == 32
-    consts = {k: int(v) for k, v in re.findall(r"#define (MICF_COMPONENTS_\w+) (\d+)", src)}
+    consts = abi_header.defines(HEADER, "MICF_COMPONENTS_")
     assert (consts["MICF_COMPONENTS_U8"], consts["MICF_COMPONENTS_I16"], consts["MICF_COMPONENTS_I32"]) == (P.IN_U8, P.IN_I16, P.IN_I32)
     assert (consts["MICF_COMPONENTS_KEEP_LARGEST"], consts["MICF_COMPONENTS_REMOVE_SMALL"]) == (P.KEEP_LARGEST, P.REMOVE_SMALL)
     assert consts["MICF_COMPONENTS_MAX_CLASSES"] == P.MAX_CLASSES == 32

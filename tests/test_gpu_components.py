@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import components_ref as C
+from tiny_model import tiny_head
 
 pytestmark = pytest.mark.gpu
 
@@ -310,25 +311,13 @@ def test_capture_and_replay_under_a_graph():
 
 # ---- end to end -----------------------------------------------------------------------------------------------------------------
 
-def _tiny_head():
-    """Head as tests/test_gpu_restore.py builds it for 32^3 (embed_dim 24, depths 1-1-1-1, the oracle's seeded fill, the output
-    convolution scaled by 20)."""
-    from micformer_amd.models.MICFormer_self import Head
-    from oracle import fill
-    model = Head(embed_dim=24, num_classes=8, depths=(1, 1, 1, 1))
-    with torch.no_grad():
-        for name, t in model.state_dict().items():
-            t.copy_(fill.fill_tensor(name, t) * (20.0 if name.startswith("out_conv.") else 1.0))
-    return model.cuda().eval()
-
-
 def test_segment_pair_with_keep_largest():
     from micformer_amd import postprocess as P, restore
     g = np.random.default_rng(41)
     shape, size = (41, 50, 37), (32, 32, 32)
     ct = torch.from_numpy(g.integers(-1000, 3000, size=shape, dtype=np.int16)).cuda()
     mr = torch.from_numpy(g.integers(0, 1500, size=shape, dtype=np.int16)).cuda()
-    model = _tiny_head()
+    model = tiny_head()
     plain = restore.segment_pair(model, ct, mr, size=size)
     clean = restore.segment_pair(model, ct, mr, size=size, keep_largest=True)
     assert clean.dtype == torch.int16 and clean.shape == plain.shape

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import restore_ref as R
+from tiny_model import tiny_head
 
 pytestmark = pytest.mark.gpu
 
@@ -222,20 +223,6 @@ def test_full_size_against_the_aten_composition(probabilities):
     assert res["ok"], res
 
 
-def _tiny_head():
-    """Head as tests/test_gpu_model.py builds it for 32^3 (embed_dim 24, depths 1-1-1-1, the oracle's seeded fill), with the output
-    convolution scaled by 20: the filled network's logits stay within +-0.53, where tau = 1e-4 (derived for magnitudes up to 12)
-    makes 4e-3 of the voxels near ties; scaled they reach +-10.6, the magnitude the rule was derived for (measured on the CPU
-    oracle: near-tie share 1.2e-4 for both interpolands, all eight classes present)."""
-    from micformer_amd.models.MICFormer_self import Head
-    from oracle import fill
-    model = Head(embed_dim=24, num_classes=8, depths=(1, 1, 1, 1))
-    with torch.no_grad():
-        for name, t in model.state_dict().items():
-            t.copy_(fill.fill_tensor(name, t) * (20.0 if name.startswith("out_conv.") else 1.0))
-    return model.cuda().eval()
-
-
 @pytest.mark.parametrize("probabilities", [False, True], ids=["logits", "probs"])
 def test_segment_pair_end_to_end(probabilities):
     from micformer_amd import data, loader, restore
@@ -243,7 +230,7 @@ def test_segment_pair_end_to_end(probabilities):
     shape, size = (41, 50, 37), (32, 32, 32)
     ct = torch.from_numpy(g.integers(-1000, 3000, size=shape, dtype=np.int16)).cuda()
     mr = torch.from_numpy(g.integers(0, 1500, size=shape, dtype=np.int16)).cuda()
-    model = _tiny_head()
+    model = tiny_head()
     # the model's own logits, copied to the host for the referee
     image, _, _ = loader.load_pair(ct, mr, None, size=size)
     x, _ = data.prepare_raw_batch(image.unsqueeze(0), None, None)

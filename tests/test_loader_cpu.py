@@ -1,20 +1,18 @@
 """CPU checks of the volume loader: the referee (tests/loader_ref.py) against the golden fixture made by the real reference loader and
-against a float64 brute force, the C-ABI of include/micformer_loader.h against the ctypes table and the library, argument errors
-caught before any launch, and the compiled device code's scratch use."""
+against a float64 brute force, the ctypes struct and constants against include/micformer_loader.h (tests/test_abi.py has the
+entry points), argument errors caught before any launch, and the compiled device code's scratch use."""
 import ctypes
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import loader_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "micformer_loader.h")
+HEADER = "micformer_loader.h"
 GOLDEN = os.path.join(ROOT, "tests", "golden", "f11_loader.npz")
 
 
@@ -68,43 +66,10 @@ def test_referee_class_map_and_crop_rules():
 
 # ---- the C-ABI --------------------------------------------------------------------------------------------------------------
 
-def parse_header():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(int64_t|int)\s+(micf_\w+)\s*\(([^)]*)\)\s*;", src):
-        sig = ""
-        for a in [a.strip() for a in m.group(3).split(",") if a.strip()]:
-            if "*" in a or a.startswith("micf_stream_t"):
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            else:
-                raise AssertionError(f"unparsed argument {a!r} in {m.group(2)}")
-        decls[m.group(2)] = (m.group(1), sig)
-    return decls
-
-
-def test_loader_header_matches_ctypes_table_and_library():
-    from micformer_amd import _lib, loader, metrics
-    d = parse_header()
-    assert set(d) == set(loader.SIGNATURES) and len(d) == 2
-    for name, (ret, sig) in d.items():
-        assert loader.SIGNATURES[name] == sig, name
-        assert (loader._RESTYPE.get(name) is _lib._L) == (ret == "int64_t"), name
-        assert name not in _lib.SIGNATURES and name not in metrics.SIGNATURES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in d:
-        assert hasattr(lib, name), f"{name} declared but not exported"
-
-
 def test_sample_struct_matches_the_header():
     from micformer_amd import loader
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef struct micf_loader_sample \{(.*?)\} micf_loader_sample;", src, flags=re.S).group(1)
     names = []
-    for decl in [d.strip() for d in body.split(";") if d.strip()]:
+    for decl in abi_header.struct_decls(HEADER, "micf_loader_sample"):
         if decl.startswith("const void*"):
             names += [(n.strip(), ctypes.c_void_p) for n in decl[len("const void*"):].split(",")]
         else:
@@ -114,10 +79,10 @@ def test_sample_struct_matches_the_header():
                 names.append((n[:-3], ctypes.c_int32 * 3) if n.endswith("[3]") else (n, ctypes.c_int32))
     assert [(n, t) for n, t in loader.LoaderSample._fields_] == names
     assert ctypes.sizeof(loader.LoaderSample) == 3 * 8 + 12 * 4
-    consts = dict(re.findall(r"#define (MICF_LOADER_\w+) (\d+)", src))
-    assert (int(consts["MICF_LOADER_I16"]), int(consts["MICF_LOADER_F32"]), int(consts["MICF_LOADER_I32"])) == (
+    consts = abi_header.defines(HEADER, "MICF_LOADER_")
+    assert (consts["MICF_LOADER_I16"], consts["MICF_LOADER_F32"], consts["MICF_LOADER_I32"]) == (
         loader.DTYPE_I16, loader.DTYPE_F32, loader.DTYPE_I32)
-    assert int(consts["MICF_LOADER_MAX_LABEL_VALUES"]) == loader.MAX_LABEL_VALUES
+    assert consts["MICF_LOADER_MAX_LABEL_VALUES"] == loader.MAX_LABEL_VALUES
 
 
 def _sample(loader, **kw):
@@ -213,18 +178,7 @@ def test_python_front_end_rejects_before_the_device():
 # ---- the device code ----------------------------------------------------------------------------------------------------------
 
 def test_volume_loader_device_code_uses_no_scratch():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_micformer_build", os.path.join(ROOT, "micformer_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
-    flags = [f for f in build.FLAGS if f != "-fPIC"]
+    sizes, asm, flags = abi_header.device_asm("volume_loader.hip")
     assert not any("fast-math" in f or "-Ofast" in f for f in flags)     # the normalisation needs the IEEE divide
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "volume_loader.s")
-        r = subprocess.run([build._hipcc()] + flags + ["-S", "--cuda-device-only", os.path.join(build.CSRC, "volume_loader.hip"),
-                                                       "-o", out], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        asm = open(out).read()
-    sizes = re.findall(r"\.amdhsa_private_segment_fixed_size\s+(\d+)", asm)
-    assert len(sizes) == 4 and all(int(s) == 0 for s in sizes), sizes
+    assert len(sizes) == 4 and all(v == 0 for v in sizes.values()), sizes
     assert "v_div_fixup_f32" in asm and "v_div_fmas_f32" in asm          # the correctly rounded fp32 divide sequence

@@ -1,20 +1,15 @@
 """CPU checks of the volume restore: the referee (tests/restore_ref.py) against a float64 brute force of the coordinate rule, the
-C-ABI of include/micformer_restore.h against the ctypes table and the library, argument errors caught before any launch, the
+ctypes struct and constants against include/micformer_restore.h (tests/test_abi.py has the entry points), argument errors caught before any launch, the
 workspace query, and the compiled device code's scratch use."""
 import ctypes
-import os
-import re
-import subprocess
-import tempfile
-
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import restore_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "micformer_restore.h")
+HEADER = "micformer_restore.h"
 
 
 # ---- the referee ----------------------------------------------------------------------------------------------------------------
@@ -59,45 +54,12 @@ def test_referee_rule_details():
 
 # ---- the C-ABI --------------------------------------------------------------------------------------------------------------
 
-def parse_header():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(int64_t|int)\s+(micf_\w+)\s*\(([^)]*)\)\s*;", src):
-        sig = ""
-        for a in [a.strip() for a in m.group(3).split(",") if a.strip()]:
-            if "*" in a or a.startswith("micf_stream_t"):
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            else:
-                raise AssertionError(f"unparsed argument {a!r} in {m.group(2)}")
-        decls[m.group(2)] = (m.group(1), sig)
-    return decls
-
-
-def test_restore_header_matches_ctypes_table_and_library():
-    from micformer_amd import _lib, loader, metrics, restore
-    d = parse_header()
-    assert set(d) == set(restore.SIGNATURES) and len(d) == 2
-    for name, (ret, sig) in d.items():
-        assert restore.SIGNATURES[name] == sig, name
-        assert (restore._RESTYPE.get(name) is _lib._L) == (ret == "int64_t"), name
-        assert name not in _lib.SIGNATURES and name not in metrics.SIGNATURES and name not in loader.SIGNATURES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in d:
-        assert hasattr(lib, name), f"{name} declared but not exported"
-
-
 def test_sample_struct_and_constants_match_the_header():
     from micformer_amd import restore
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef struct micf_restore_sample \{(.*?)\} micf_restore_sample;", src, flags=re.S).group(1)
-    assert [d.strip() for d in body.split(";") if d.strip()] == ["void* out", "int32_t out_shape[3]"]
+    assert abi_header.struct_decls(HEADER, "micf_restore_sample") == ["void* out", "int32_t out_shape[3]"]
     assert [(n, t) for n, t in restore.RestoreSample._fields_] == [("out", ctypes.c_void_p), ("out_shape", ctypes.c_int32 * 3)]
     assert ctypes.sizeof(restore.RestoreSample) == 24
-    consts = {k: int(v) for k, v in re.findall(r"#define (MICF_RESTORE_\w+) (\d+)", src)}
+    consts = abi_header.defines(HEADER, "MICF_RESTORE_")
     assert (consts["MICF_RESTORE_U8"], consts["MICF_RESTORE_I16"], consts["MICF_RESTORE_I32"]) == (
         restore.OUT_U8, restore.OUT_I16, restore.OUT_I32)
     assert (consts["MICF_RESTORE_LOGITS"], consts["MICF_RESTORE_PROBS"]) == (restore.LOGITS, restore.PROBS)
@@ -198,22 +160,10 @@ def test_python_front_end_rejects_before_the_device():
 # ---- the device code ----------------------------------------------------------------------------------------------------------
 
 def test_volume_restore_device_code_uses_no_scratch():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("_micformer_build", os.path.join(ROOT, "micformer_amd", "build.py"))
-    build = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(build)
-    assert "volume_restore.hip" in build.SOURCES
-    flags = [f for f in build.FLAGS if f != "-fPIC"]
+    kernels, asm, flags = abi_header.device_asm("volume_restore.hip")
     assert not any("fast-math" in f or "-Ofast" in f for f in flags)     # the softmax pre-pass needs the IEEE divide
-    with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "volume_restore.s")
-        r = subprocess.run([build._hipcc()] + flags + ["-S", "--cuda-device-only", os.path.join(build.CSRC, "volume_restore.hip"),
-                                                       "-o", out], capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr
-        asm = open(out).read()
-    kernels = dict(re.findall(r"\.amdhsa_kernel\s+(\S+).*?\.amdhsa_private_segment_fixed_size\s+(\d+)", asm, flags=re.S))
     fused = [k for k in kernels if "restore_fused_kernel" in k]
     assert len(kernels) == 4 and len(fused) == 3, sorted(kernels)          # softmax + the fused kernel for uint8 / int16 / int32
-    assert all(int(v) == 0 for v in kernels.values()), kernels
+    assert all(v == 0 for v in kernels.values()), kernels
     assert "scratch_" not in asm and "flat_load" not in asm                # the taps are global loads, nothing spills
     assert "atomic" not in asm                                             # bit-identical from run to run

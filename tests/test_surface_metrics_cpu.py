@@ -1,18 +1,12 @@
 """CPU checks of the surface metrics: the referee (tests/surface_metrics_ref.py) against brute force and against scipy, the
-C-ABI of include/micformer_metrics.h against the ctypes table and the library, and argument errors caught before any launch."""
-import ctypes
+workspace queries of include/micformer_metrics.h (tests/test_abi.py has the entry points), and argument errors caught before any launch."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import surface_metrics_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "micformer_metrics.h")
 
 
 def _shell(shape, centre, r0, r1):
@@ -124,39 +118,6 @@ def test_referee_iou_rules():
 
 
 # ---- the C-ABI --------------------------------------------------------------------------------------------------------------
-
-def parse_header():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(int64_t|int)\s+(micf_\w+)\s*\(([^)]*)\)\s*;", src):
-        sig = ""
-        for a in [a.strip() for a in m.group(3).split(",") if a.strip()]:
-            if "*" in a or a.startswith("micf_stream_t"):
-                sig += "p"
-            elif a.startswith("int64_t"):
-                sig += "l"
-            elif a.startswith("int "):
-                sig += "i"
-            elif a.startswith("double "):
-                sig += "d"
-            else:
-                raise AssertionError(f"unparsed argument {a!r} in {m.group(2)}")
-        decls[m.group(2)] = (m.group(1), sig)
-    return decls
-
-
-def test_metrics_header_matches_ctypes_table_and_library():
-    from micformer_amd import _lib, metrics
-    d = parse_header()
-    assert set(d) == set(metrics.SIGNATURES)
-    for name, (ret, sig) in d.items():
-        assert metrics.SIGNATURES[name] == sig, name
-        assert (metrics._RESTYPE.get(name) is _lib._L) == (ret == "int64_t"), name
-        assert name not in _lib.SIGNATURES
-    lib = ctypes.CDLL(_lib.LIB_PATH)
-    for name in d:
-        assert hasattr(lib, name), f"{name} declared but not exported"
-
 
 def test_workspace_queries_are_pure_and_validate():
     from micformer_amd.metrics import lib
