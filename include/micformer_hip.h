@@ -493,7 +493,12 @@ typedef struct micf_block_fwd_group {
   void* h;             /* fc1 pre-activation [T, hidden]: float for MICF_DTYPE_F32, bf16 (uint16_t, round-to-nearest-even)
                           for MICF_DTYPE_BF16 -- only micf_block_bwd reads it (GELU'), so the bf16 mode stores it at half width.
                           May be NULL on the tile-per-workgroup kernels (micf_block_fuses_sampler != 0): not written (8 of the 36 bytes a bf16 block
-                          writes per element of T*C); micf_block_bwd then rebuilds it from xn2 with one more GEMM phase */
+                          writes per element of T*C); micf_block_bwd then rebuilds it from xn2 with one more GEMM phase.
+                          WAVE-PRIVATE kernels (C = 48, head_dim 16, MICF_DTYPE_BF16, option "block_wave" on, T * C * 4 < 2^32): h
+                          may be NULL whatever micf_block_recomputes_h says, and q and kv may be NULL TOGETHER with it (14 of
+                          the 45 bytes per element not written): micf_block_bwd rebuilds all three in registers from xn2 / xn /
+                          kvs16, bit for bit (micf_block_bwd_group.xn).  q == NULL without kv == NULL and h == NULL, or on any
+                          other kernel, is MICF_EINVAL */
   float* g;            /* GELU(h) [T, hidden] (operand of the fc2 weight gradient) */
   float* stats;        /* [4, T]: mean1, rstd1, mean2, rstd2 */
   void* kvs16;         /* cross, bf16 storage only (micf_block_saves_bf16): [T, C] bf16 copy of the K/V source, the operand of the kv
@@ -527,8 +532,9 @@ int micf_block_saves_bf16(int C, int heads, int dtype);
 typedef struct micf_block_bwd_group {
   const float* dy;     /* [T, C] gradient w.r.t. the block output (also fc2's output gradient for the weight-gradient GEMM) */
   const float *x, *x1, *stats, *q, *kv; /* as saved by micf_block_fwd (x and ln1_g may be NULL for a cross block) */
-  const void* h;       /* ... float or bf16 by dtype, as micf_block_fwd wrote it; NULL (micf_block_recomputes_h only) = rebuild it
-                          in the kernel as xn2 W1^T + b1 from the three fields at the end of this struct */
+  const void* h;       /* ... float or bf16 by dtype, as micf_block_fwd wrote it; NULL (micf_block_recomputes_h, or wherever the
+                          wave-private kernels run: see q == NULL at the end of this struct) = rebuild it in the kernel as
+                          xn2 W1^T + b1 from xn2 / w1 / b1 below */
   const float *ln1_g, *ln2_g;
   const void *wqt, *wkvt, *wpt, *w1t, *w2t;  /* TRANSPOSED weights: q^T [C,C], kv^T [C,2C], proj^T [C,C], fc1^T [C,hidden],
                                                 fc2^T [hidden,C] from micf_weight_prep_grouped (dst_t), K16-blocked:
@@ -557,6 +563,14 @@ typedef struct micf_block_bwd_group {
   const float *pre_mean, *pre_rstd; /* [T] its saved statistics */
   const float* pre_g;    /* [C] its gain */
   float* pre_part;       /* out [tiles, 2C]: per-tile partial dgamma | dbeta of that LayerNorm (micf_layernorm_bwd_finish) */
+  /* q == NULL (with kv == NULL and h == NULL, both groups alike; wave-private kernels only: C = 48, head_dim 16,
+   * MICF_DTYPE_BF16, option "block_wave" on -- MICF_EINVAL anywhere else, before any launch): q, k | v are rebuilt in the kernel,
+   * bit for bit as micf_block_fwd would have stored them, from the six fields below (read only then; all non-NULL and 16-byte
+   * aligned, kvs16 for a cross block only).  h is rebuilt from xn2 / w1 / b1 above. */
+  const void* xn;        /* LN1(x) [T, C] bf16 as micf_block_fwd saved it */
+  const void* kvs16;     /* cross: the bf16 copy of the K/V source [T, C] as micf_block_fwd saved it */
+  const void *wq, *wkv;  /* attn.q.weight [C, C], attn.kv.weight [2C, C]: the forward's K16-blocked bf16 shadow copies (micf_block_fwd_group.wq / .wkv) */
+  const float *bq, *bkv; /* attn.q.bias [C], attn.kv.bias [2C] */
 } micf_block_bwd_group;
 /* != 0: the caller should pass h == NULL in both groups structs (see there).  Only with the option "block_recompute_h" set
  * (micf_set_option) and only for the tile-per-workgroup kernels (everything but the few-token decomposition at C = 384 / head_dim 16): a memory

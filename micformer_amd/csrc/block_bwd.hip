@@ -657,20 +657,34 @@ extern "C" int micf_block_bwd(const micf_block_bwd_group* groups, int ngroups, i
   if (TM == 0) return MICF_EUNSUPPORTED;
   if (dtype != MICF_DTYPE_F32 && dtype != MICF_DTYPE_BF16) return MICF_EINVAL;
   BlkBwdArgs a;
+  // the launch takes the wave-private kernel (block_wave_bwd.h; the dispatch below): the C = 48 stages in bf16 mode, both groups of
+  // one kind.  Only there may q | kv be rebuilt, and h whatever micf_block_recomputes_h says.
+  const micf_block_bwd_group& g0 = groups[0], &g1 = groups[ngroups - 1];
+  const bool wave = options().block_wave != 0 && C == 48 && C / heads == 16 && TM == 32 && dtype == MICF_DTYPE_BF16 &&
+                    (g0.dxs != nullptr) == (g1.dxs != nullptr) && (g0.pre_d != nullptr) == (g1.pre_d != nullptr) && !(g0.dxs && g0.pre_d) &&
+                    (int64_t)B * D * H * W * hidden * 2 < ((int64_t)1 << 31);
   for (int i = 0; i < ngroups; ++i) {
     const micf_block_bwd_group& g = groups[i];
-    const void* need[] = {g.dy, g.x1, g.stats, g.q, g.kv, g.ln2_g, g.wqt, g.wkvt, g.wpt, g.w1t, g.w2t, g.dx, g.dx1, g.dh, g.dq, g.dkv};
+    const void* need[] = {g.dy, g.x1, g.stats, g.ln2_g, g.wqt, g.wkvt, g.wpt, g.w1t, g.w2t, g.dx, g.dx1, g.dh, g.dq, g.dkv};
     for (const void* p : need)
       if (!p || (reinterpret_cast<uintptr_t>(p) & 15)) return MICF_EINVAL;
     if (g.h) {                                          // the saved pre-activation ...
       if (reinterpret_cast<uintptr_t>(g.h) & 15) return MICF_EINVAL;
-    } else {                                            // ... or what the kernel rebuilds it from (tile kernels only, both groups alike)
+    } else {                                            // ... or what the kernel rebuilds it from (both groups alike)
       const void* re[] = {g.xn2, g.w1, g.b1};
       for (const void* p : re)
         if (!p || (reinterpret_cast<uintptr_t>(p) & 15)) return MICF_EINVAL;
-      if (!micf_block_recomputes_h(C, heads)) return MICF_EINVAL;
+      if (!wave && !micf_block_recomputes_h(C, heads)) return MICF_EINVAL;
     }
-    if (i > 0 && (g.h == nullptr) != (groups[0].h == nullptr)) return MICF_EINVAL;
+    if (g.q) {                                          // the saved q, k | v ...
+      if (!g.kv || ((reinterpret_cast<uintptr_t>(g.q) | reinterpret_cast<uintptr_t>(g.kv)) & 15)) return MICF_EINVAL;
+    } else {                                            // ... or rebuilt too (wave-private kernels only: together, and only with h)
+      if (g.kv || g.h || !wave) return MICF_EINVAL;
+      const void* re[] = {g.xn, g.wq, g.wkv, g.bq, g.bkv, g.dxs ? g.kvs16 : g.xn};
+      for (const void* p : re)
+        if (!p || (reinterpret_cast<uintptr_t>(p) & 15)) return MICF_EINVAL;
+    }
+    if (i > 0 && ((g.h == nullptr) != (groups[0].h == nullptr) || (g.q == nullptr) != (groups[0].q == nullptr))) return MICF_EINVAL;
     if (g.pre_d) {                                      // LayerNorm-backward prologue: self block, tile kernels, bf16 storage
       const void* pr[] = {g.pre_d, g.pre_x, g.pre_mean, g.pre_rstd, g.pre_g, g.pre_part, g.dy16};
       for (const void* p : pr)
@@ -695,11 +709,10 @@ extern "C" int micf_block_bwd(const micf_block_bwd_group* groups, int ngroups, i
   if ((int64_t)2 * H * W * (TM / 8 + 1) * hidden * (int64_t)sizeof(float) >= (int64_t)1 << 32) return MICF_EUNSUPPORTED;
   if (block_wide_tile_tokens(C, hd)) return block_bwd_wide(groups, ngroups, B, D, H, W, C, heads, scale, dtype, s);
   // the C = 48 stages in bf16 mode: one wave per 32-token tile, nothing exchanged through LDS (block_wave_bwd.h); the test hook
-  // "block_wave" = 0 keeps the tile-per-workgroup kernel (which also serves the fp32 mode and the recomputed h)
+  // "block_wave" = 0 keeps the tile-per-workgroup kernel (which also serves the fp32 mode, and rebuilds h -- never q | kv -- with
+  // one more GEMM phase where micf_block_recomputes_h says so)
   {
-    if (options().block_wave != 0 && C == 48 && hd == 16 && tj == 2 && dtype == MICF_DTYPE_BF16 && a.attn_mfma && a.g[0].h && a.g[1].h && (a.g[0].dxs != nullptr) == (a.g[1].dxs != nullptr) &&
-        (a.g[0].pre_d != nullptr) == (a.g[1].pre_d != nullptr) && !(a.g[0].dxs && a.g[0].pre_d) &&
-        a.geo.T * (int64_t)hidden * 2 < ((int64_t)1 << 31))
+    if (wave)
     {
       if (options().block_debug & 1) a.attn_mfma |= 2;         // (probe: the wave kernel stores nothing)
       return wave48::launch_bwd_wave48(a, s);

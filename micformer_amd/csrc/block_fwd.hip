@@ -550,6 +550,8 @@ extern "C" int micf_block_saves_bf16(int C, int heads, int dtype) {
   return block_saves_bf16(C, C / heads, dtype) ? 1 : 0;
 }
 
+static bool cross_group(const micf_block_fwd_group& g) { return g.kvsrc != nullptr || g.hid != nullptr; }
+
 extern "C" int micf_block_fwd(const micf_block_fwd_group* groups, int ngroups, int B, int D, int H, int W, int C, int heads,
                               int hidden, float eps, float scale, int dtype, micf_stream_t stream) {
   if (!groups || ngroups < 1 || ngroups > 2) return MICF_EINVAL;
@@ -563,6 +565,10 @@ extern "C" int micf_block_fwd(const micf_block_fwd_group* groups, int ngroups, i
   // INFERENCE FORM: every saved-tensor pointer of every group NULL -> the launch writes y only (4 instead of 40 bytes per element of
   // T * C in bf16 mode); tile-per-workgroup and wave-private kernels (not the few-token decomposition, which re-reads its own saves)
   int nosave = -1;
+  // the launch takes the wave-private kernel (the dispatch below) -- the only place where q / kv / h may stay unwritten for a backward
+  // that rebuilds them (block_wave_bwd.h)
+  const bool wave = options().block_wave != 0 && C == 48 && C / heads == 16 && dtype == MICF_DTYPE_BF16 && !att8 &&
+                    !(options().block_debug & ~17) && (int64_t)B * D * H * W * C * 4 < ((int64_t)1 << 32);
   for (int i = 0; i < ngroups; ++i) {
     const micf_block_fwd_group& g = groups[i];
     const void* must[] = {g.x, g.ln1_g, g.ln1_b, g.wq, g.bq, g.wkv, g.bkv, g.wp, g.bp, g.ln2_g, g.ln2_b, g.w1, g.b1, g.w2, g.b2, g.y};
@@ -577,10 +583,14 @@ extern "C" int micf_block_fwd(const micf_block_fwd_group* groups, int ngroups, i
     if (ns) {
       if (block_wide_tile_tokens(C, C / heads)) return MICF_EUNSUPPORTED;
     } else {
-      for (const void* p : saves)
-        if (!p || (reinterpret_cast<uintptr_t>(p) & 15)) return MICF_EINVAL;
-      // h may be left out where the backward rebuilds it (micf_block_recomputes_h); the few-token decomposition always stores it
-      if (g.h ? (reinterpret_cast<uintptr_t>(g.h) & 15) != 0 : !micf_block_recomputes_h(C, heads)) return MICF_EINVAL;
+      const bool noqkv = !g.q && !g.kv && !g.h && wave;      // (q | kv rebuilt by the wave-private backward: together, and only with h)
+      for (int k = 0; k < 7; ++k)                           // (saves[0], saves[1] = q, kv)
+        if ((!saves[k] && !(noqkv && k < 2)) || (reinterpret_cast<uintptr_t>(saves[k]) & 15)) return MICF_EINVAL;
+      if (noqkv && (!g.xn || (cross_group(g) && !g.kvs16))) return MICF_EINVAL;      // (... from these)
+      if (i > 0 && (g.q == nullptr) != (groups[0].q == nullptr)) return MICF_EINVAL;
+      // h may be left out where the backward rebuilds it (micf_block_recomputes_h, or the wave-private kernels); the few-token
+      // decomposition always stores it
+      if (g.h ? (reinterpret_cast<uintptr_t>(g.h) & 15) != 0 : !(wave || micf_block_recomputes_h(C, heads))) return MICF_EINVAL;
     }
     if ((g.kvsrc && (reinterpret_cast<uintptr_t>(g.kvsrc) & 15)) || (g.xn && (reinterpret_cast<uintptr_t>(g.xn) & 15)) ||
         (g.kvs16 && (reinterpret_cast<uintptr_t>(g.kvs16) & 15))) return MICF_EINVAL;
@@ -611,8 +621,7 @@ extern "C" int micf_block_fwd(const micf_block_fwd_group* groups, int ngroups, i
   if (block_wide_tile_tokens(C, hd)) return block_fwd_wide(groups, ngroups, B, D, H, W, C, heads, eps, scale, att8 ? MICF_DTYPE_BF16_ATTN_FP8 : dtype, s);   // (the few-token F1: attention on the matrix cores in both bf16 modes)
   // the C = 48 stages in bf16 mode: one wave per 16 tokens, nothing exchanged through LDS (block_wave_fwd.h); the test hook
   // "block_wave" = 0 keeps the tile-per-workgroup kernel (which also serves the fp32 mode, the fp8 attention and the probe flags)
-  if (options().block_wave != 0 && C == 48 && hd == 16 && dtype == MICF_DTYPE_BF16 && a.att8 == 1 && !(a.debug & ~17) &&
-      a.geo.T * (int64_t)C * 4 < ((int64_t)1 << 32))          // (the fused sampling addresses its tap rows with 32-bit byte offsets)
+  if (wave)                                                // (T * C * 4 < 2^32: the fused sampling addresses its tap rows with 32-bit byte offsets)
     return wave48::launch_fwd_wave48(a, s);
 #define MICF_BF(C_, HD_, TJ_) if (C == C_ && hd == HD_ && tj == TJ_) return launch_fwd<C_, HD_, TJ_>(a, dtype, s)
   MICF_BF(48, 16, 2); MICF_BF(96, 16, 1); MICF_BF(192, 16, 1);

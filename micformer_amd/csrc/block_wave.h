@@ -23,6 +23,25 @@ __device__ __forceinline__ bf16x8 frag32(const char* lds, int base, int f, int l
 __device__ __forceinline__ bf16x4_t frag16(const char* lds, int base, int f, int lane) {
   return *reinterpret_cast<const bf16x4_t*>(lds + base + (f * 64 + lane) * 8);
 }
+// The forward-orientation fragments BOTH kernels stage (the forward for its own products, the backward to rebuild q / k / v and the
+// fc1 pre-activation bit for bit: same fragments, same products, same rounding).  q | k | v: nine 16-row blocks (q 0..2, k 3..5,
+// v 6..8) in natural row order, k = 0..31 at b32 and k = 32..47 at b16; fc1: twelve blocks with the rows in layout P.
+__device__ __forceinline__ void stage_qkv_fwd(char* lds, int b32, int b16, const uint16_t* wq, const uint16_t* wkv, int tid, int nthr) {
+  for (int s = tid; s < 9 * 64; s += nthr) {
+    const int j = s >> 6, li = s & 15, lr = (s >> 4) & 3;
+    const uint16_t* W = j < 3 ? wq : wkv;
+    const int row = 16 * (j < 3 ? j : j - 3) + li;
+    *reinterpret_cast<u32x4v*>(lds + b32 + s * 16) = *reinterpret_cast<const u32x4v*>(W + k16(row, 8 * lr, 3));
+    *reinterpret_cast<u32x2v*>(lds + b16 + s * 8) = *reinterpret_cast<const u32x2v*>(W + k16(row, 32 + 4 * lr, 3));
+  }
+}
+__device__ __forceinline__ void stage_fc1_fwd(char* lds, int b32, int b16, const uint16_t* w1, int tid, int nthr) {
+  for (int s = tid; s < 12 * 64; s += nthr) {
+    const int j = s >> 6, li = s & 15, lr = (s >> 4) & 3, row = row_p192(j, li);
+    *reinterpret_cast<u32x4v*>(lds + b32 + s * 16) = *reinterpret_cast<const u32x4v*>(w1 + k16(row, 8 * lr, 3));
+    *reinterpret_cast<u32x2v*>(lds + b16 + s * 8) = *reinterpret_cast<const u32x2v*>(w1 + k16(row, 32 + 4 * lr, 3));
+  }
+}
 __device__ __forceinline__ f32x4 mfma32(const bf16x8& a, const bf16x8& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4 mfma16(const bf16x4_t& a, const bf16x4_t& b, const f32x4& c) { return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0); }
 // A 16x16x16 product must not take the accumulator of the 16x16x32 product issued right before it: on gfx950 that back-to-back

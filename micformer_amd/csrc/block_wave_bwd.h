@@ -25,11 +25,27 @@ constexpr int kBPh = kBP + 3 * 1024;             //                            [
 constexpr int kBQ = kBPh + 3 * 512;              // q^T [48 rows, k = 48 in heads]:  [3][3][64] x 8 B
 constexpr int kBKV = kBQ + 9 * 512;              // kv^T [48 rows, k = 96 in heads]: [3][6][64] x 8 B
 constexpr int kBVec = kBKV + 18 * 512;           // floats: ln1_g | ln2_g | pre_g
-constexpr int kBPark = kBVec + 3 * C * 4;          // per wave: a [16 tokens][48 channels] fp32 tile in layout P (wave-private: no barrier)
+// REBUILD forms (template parameter RB of the kernel; micf_block_bwd_group.h / .q NULL): what the forward did not store is
+// recomputed from the forward's own fragments (block_wave.h::stage_fc1_fwd / stage_qkv_fwd) --
+//   RB >= 1: fc1 in forward orientation [12][64] x 16 B + [12][64] x 8 B, then b1 (192 floats)           (+ 19 200 B)
+//   RB == 2: q | k | v in forward orientation [9][64] x 16 B + [9][64] x 8 B, then bq | bkv (144 floats) (+ 14 400 B)
+// and then, per wave, the park tile.  Two 8-wave workgroups per CU no longer fit beside that, so the rebuild forms run ONE 16-wave
+// workgroup per CU (the same 16 resident waves; 126 528 / 140 928 B of the 160 KiB).
+constexpr int kBRF32 = kBVec + 3 * C * 4;
+constexpr int kBRF16 = kBRF32 + 12 * 1024;
+constexpr int kBRB1 = kBRF16 + 12 * 512;
+constexpr int kBRQ32 = kBRB1 + HID * 4;
+constexpr int kBRQ16 = kBRQ32 + 9 * 1024;
+constexpr int kBRBq = kBRQ16 + 9 * 512;
+constexpr int bwd_waves(int rb) { return rb ? 16 : NWAVE; }
+constexpr int bwd_park(int rb) { return rb == 0 ? kBRF32 : (rb == 1 ? kBRQ32 : kBRBq + 3 * C * 4); }   // per wave: a [16 tokens][48 channels] fp32 tile in layout P (wave-private: no barrier)
 constexpr int kParkFloats = 4 * (16 * 12 + 8);     // slot of (lane group lr, token li, value e): lr * 200 + li * 12 + e (8 floats of padding per lane group: banks)
-constexpr int kBwdLdsBytes = kBPark + NWAVE * kParkFloats * 4;
+constexpr int bwd_lds_bytes(int rb) { return bwd_park(rb) + bwd_waves(rb) * kParkFloats * 4; }
+static_assert(bwd_lds_bytes(0) == 81472 && 2 * bwd_lds_bytes(0) <= 160 * 1024 && bwd_lds_bytes(2) <= 160 * 1024, "LDS budget of the wave-private backward");
 
+template <int RB>
 __device__ __forceinline__ void stage_weights_bwd(char* lds, const micf_block_bwd_group& g) {
+  constexpr int NTHR = 64 * bwd_waves(RB);
   const uint16_t* wqt = static_cast<const uint16_t*>(g.wqt), *wkvt = static_cast<const uint16_t*>(g.wkvt), *wpt = static_cast<const uint16_t*>(g.wpt),
                  *w1t = static_cast<const uint16_t*>(g.w1t), *w2t = static_cast<const uint16_t*>(g.w2t);
   const int tid = threadIdx.x;
@@ -59,6 +75,16 @@ __device__ __forceinline__ void stage_weights_bwd(char* lds, const micf_block_bw
   for (int e = tid; e < 3 * C; e += NTHR) {
     const float* src = e < C ? g.ln1_g : (e < 2 * C ? g.ln2_g : g.pre_g);
     PV[e] = src ? src[e % C] : 0.f;
+  }
+  if (RB >= 1) {
+    stage_fc1_fwd(lds, kBRF32, kBRF16, static_cast<const uint16_t*>(g.w1), tid, NTHR);
+    float* b1 = reinterpret_cast<float*>(lds + kBRB1);
+    for (int e = tid; e < HID; e += NTHR) b1[e] = g.b1[e];
+  }
+  if (RB == 2) {
+    stage_qkv_fwd(lds, kBRQ32, kBRQ16, static_cast<const uint16_t*>(g.wq), static_cast<const uint16_t*>(g.wkv), tid, NTHR);
+    float* bq = reinterpret_cast<float*>(lds + kBRBq);      // bq | bkv: block j of q | k | v reads its bias at 16 j
+    for (int e = tid; e < 3 * C; e += NTHR) bq[e] = e < C ? g.bq[e] : g.bkv[e - C];
   }
 }
 
@@ -118,15 +144,19 @@ __device__ __forceinline__ void unpack8(const u32x4v& u, float (&o)[8]) {
 
 // CROSS / PRE: both groups of the launch alike (the entry point falls back to the tile kernel otherwise): every path the other kinds
 // need is compiled out -- a kernel that carried all three at once spilled 44 registers.
-template <bool CROSS, bool PRE>
-__global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4))) block_bwd_wave48_kernel(const BlkBwdArgs a) {
+// RB: 0 = h, q, k | v as the forward saved them; 1 = h rebuilt from xn2 (24 registers of saved h become the 6 of the xn2 row);
+// 2 = also q, k, v rebuilt per head from xn (cross: k, v from kvs16) instead of three loads behind this group's stores.  Rebuilt
+// values are the forward's bit for bit (same fragments, mfma48, bias add and rounding), so all three forms return the same bits.
+template <bool CROSS, bool PRE, int RB>
+__global__ void __launch_bounds__(64 * bwd_waves(RB)) __attribute__((amdgpu_waves_per_eu(4, 4))) block_bwd_wave48_kernel(const BlkBwdArgs a) {
+  constexpr int NWAVE = bwd_waves(RB), kBPark = bwd_park(RB);
   extern __shared__ __attribute__((aligned(1024))) char wlds[];
   const unsigned bid = blockIdx.x;
   int grp, wg, nwg;
   if (a.G == 2) { const int xcd = bid & 7; grp = xcd >> 2; wg = (int)(bid >> 3) * 4 + (xcd & 3); nwg = (int)(gridDim.x >> 3) * 4; }
   else { grp = 0; wg = bid; nwg = gridDim.x; }
   const micf_block_bwd_group& g = a.g[grp];
-  stage_weights_bwd(wlds, g);
+  stage_weights_bwd<RB>(wlds, g);
   const int tid = threadIdx.x, lane0 = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const float* PV = reinterpret_cast<const float*>(wlds + kBVec);
   const float *p_ln1g = PV, *p_ln2g = PV + C, *p_preg = PV + 2 * C;
@@ -179,15 +209,22 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
       const bf16x4_t dyB = dy.hi();
       // (the fp32 rows wait in the wave's LDS tile until dx1 = dy + ...: 12 registers the MLP phase and the second half's loads need)
       park12(tile, lr, li, dy.v);
-      // ---- the saved fc1 pre-activation (8 consecutive features per lane and block pair)
+      // ---- the saved fc1 pre-activation (8 consecutive features per lane and block pair), or the xn2 row it is rebuilt from: the
+      // B fragments the forward held
       u32x4v hreg[6];
-      {
+      bf16x8 n2A = {};
+      bf16x4_t n2B = {};
+      if (RB == 0) {
         const uint16_t* hp = static_cast<const uint16_t*>(g.h);
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
           hreg[c] = *reinterpret_cast<const u32x4v*>(at32(hp, (tk * HID + 32 * c + 8 * lr) * 2u));
           if (!live) hreg[c] = u32x4v{0u, 0u, 0u, 0u};
         }
+      } else {
+        const uint16_t* np = reinterpret_cast<const uint16_t*>(g.xn2);
+        n2A = *reinterpret_cast<const bf16x8*>(at32(np, (rowC + 8 * lr) * 2u));
+        n2B = *reinterpret_cast<const bf16x4_t*>(at32(np, (rowC + 32 + 4 * lr) * 2u));
       }
 
       // ---- MLP backward: per 32-wide chunk of the hidden features dh = s2 (dy W2) GELU'(h) (saved), dxn2 += dh W1
@@ -199,7 +236,21 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
           float h8[8];
-          unpack8(hreg[c], h8);
+          if (RB == 0) {
+            unpack8(hreg[c], h8);
+          } else {                                       // block_wave_fwd.h's fc1: the same two products, bias add and rounding
+            float4 hv[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+              const int j = 2 * c + u;
+              const f32x4 acc = mfma48(frag32(wlds, kBRF32, j, lane), frag16(wlds, kBRF16, j, lane), n2A, n2B);
+              const float4 bs = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(wlds + kBRB1) + 32 * c + 8 * lr + 4 * u);
+              hv[u] = make_float4(acc[0] + bs.x, acc[1] + bs.y, acc[2] + bs.z, acc[3] + bs.w);
+            }
+            u32x4v hq = __builtin_bit_cast(u32x4v, to_bf16x8(hv[0], hv[1]));
+            if (!live) hq = u32x4v{0u, 0u, 0u, 0u};
+            unpack8(hq, h8);
+          }
           float4 dv[2];
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
@@ -220,13 +271,41 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
       const uint16_t* qp = reinterpret_cast<const uint16_t*>(g.q);
       const uint16_t* kp = reinterpret_cast<const uint16_t*>(g.kv);
       bf16x4_t qn, kn, vn;
+      bf16x8 xnA = {}, kvA = {};
+      bf16x4_t xnB = {}, kvB = {};
       auto load_head = [&](int h) {
+        if (RB == 2) {                                   // block_wave_fwd.h's q | k | v blocks of head h
+          bf16x4_t r[3];
+#pragma unroll
+          for (int t = 0; t < 3; ++t) {
+            const int j = 3 * t + h;
+            const bool own = t == 0 || !cross;
+            const f32x4 acc = mfma48(frag32(wlds, kBRQ32, j, lane), frag16(wlds, kBRQ16, j, lane), own ? xnA : kvA, own ? xnB : kvB);
+            const float4 bs = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(wlds + kBRBq) + 16 * j + 4 * lr);
+            r[t] = pack4q(f32x4{acc[0] + bs.x, acc[1] + bs.y, acc[2] + bs.z, acc[3] + bs.w});
+          }
+          qn = r[0]; kn = r[1]; vn = r[2];
+          if (!live) { qn = bf16x4_t{0, 0, 0, 0}; kn = qn; vn = qn; }
+          return;
+        }
         qn = *reinterpret_cast<const bf16x4_t*>(at32(qp, (rowC + 16 * h + 4 * lr) * 2u));
         kn = *reinterpret_cast<const bf16x4_t*>(at32(kp, (2 * rowC + 16 * h + 4 * lr) * 2u));
         vn = *reinterpret_cast<const bf16x4_t*>(at32(kp, (2 * rowC + C + 16 * h + 4 * lr) * 2u));
         if (!live) { qn = bf16x4_t{0, 0, 0, 0}; kn = qn; vn = qn; }
       };
-      load_head(0);
+      // RB == 2: the rows q, k, v are rebuilt from instead (requested here, not with dy: the MLP phase has no registers to spare)
+      if (RB == 2) {
+        const uint16_t* xp = reinterpret_cast<const uint16_t*>(g.xn);
+        xnA = *reinterpret_cast<const bf16x8*>(at32(xp, (rowC + 8 * lr) * 2u));
+        xnB = *reinterpret_cast<const bf16x4_t*>(at32(xp, (rowC + 32 + 4 * lr) * 2u));
+        if (cross) {
+          const uint16_t* sp = static_cast<const uint16_t*>(g.kvs16);
+          kvA = *reinterpret_cast<const bf16x8*>(at32(sp, (rowC + 8 * lr) * 2u));
+          kvB = *reinterpret_cast<const bf16x4_t*>(at32(sp, (rowC + 32 + 4 * lr) * 2u));
+        }
+      } else {
+        load_head(0);
+      }
       Row12 x1;
       x1.load(at32(g.x1, rowC * 4u), lr);
       float mu2 = *at32(g.stats, (2 * T + tk) * 4u), rs2 = *at32(g.stats, (3 * T + tk) * 4u);
@@ -274,9 +353,10 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
         uint16_t* dko = reinterpret_cast<uint16_t*>(g.dkv);
 #pragma unroll
         for (int h = 0; h < 3; ++h) {
+          if (RB == 2) load_head(h);                     // (rebuilt where it is used: nothing to request ahead)
           const bf16x4_t qcur = qn, kf = kn, vf = vn;
-          if (h < 2) load_head(h + 1);
-          else if (!cross) {
+          if (RB != 2 && h < 2) load_head(h + 1);
+          if (h == 2 && !cross) {
             x.load(at32(g.x, rowC * 4u), lr);
             mu1 = *at32(g.stats, tk * 4u); rs1 = *at32(g.stats, (T + tk) * 4u);
             if (!live) { x.zero(); mu1 = 0.f; rs1 = 0.f; }
@@ -378,21 +458,33 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
   }
 }
 
-static int launch_bwd_wave48(const BlkBwdArgs& a, hipStream_t s) {
-  int nwg = (a.tiles + NWAVE - 1) / NWAVE;
-  if (nwg > 256) nwg = 256;
+template <bool CROSS, bool PRE, int RB>
+static void launch_bwd_wave48_form(const BlkBwdArgs& a, hipStream_t s) {
+  constexpr int NW = bwd_waves(RB);
+  int nwg = (a.tiles + NW - 1) / NW;
+  if (nwg > 2048 / NW) nwg = 2048 / NW;                  // 16 resident waves per CU for each of the two groups: one resident round
   const unsigned grid = a.G == 2 ? (unsigned)((nwg + 3) / 4 * 8) : (unsigned)nwg;
   static std::once_flag once;
   std::call_once(once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&block_bwd_wave48_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&block_bwd_wave48_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&block_bwd_wave48_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&block_bwd_wave48_kernel<CROSS, PRE, RB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   });
+  hipLaunchKernelGGL((block_bwd_wave48_kernel<CROSS, PRE, RB>), dim3(grid), dim3(64 * NW), bwd_lds_bytes(RB), s, a);
+}
+
+template <int RB>
+static int launch_bwd_wave48_rb(const BlkBwdArgs& a, hipStream_t s) {
   const bool cross = a.g[0].dxs != nullptr, pre = a.g[0].pre_d != nullptr;
-  if (cross) hipLaunchKernelGGL((block_bwd_wave48_kernel<true, false>), dim3(grid), dim3(NTHR), kBwdLdsBytes, s, a);
-  else if (pre) hipLaunchKernelGGL((block_bwd_wave48_kernel<false, true>), dim3(grid), dim3(NTHR), kBwdLdsBytes, s, a);
-  else hipLaunchKernelGGL((block_bwd_wave48_kernel<false, false>), dim3(grid), dim3(NTHR), kBwdLdsBytes, s, a);
+  if (cross) launch_bwd_wave48_form<true, false, RB>(a, s);
+  else if (pre) launch_bwd_wave48_form<false, true, RB>(a, s);
+  else launch_bwd_wave48_form<false, false, RB>(a, s);
   MICF_RETURN_LAUNCH();
+}
+
+// (both groups alike in h / q: checked by the entry point)
+static int launch_bwd_wave48(const BlkBwdArgs& a, hipStream_t s) {
+  if (a.g[0].q == nullptr) return launch_bwd_wave48_rb<2>(a, s);
+  if (a.g[0].h == nullptr) return launch_bwd_wave48_rb<1>(a, s);
+  return launch_bwd_wave48_rb<0>(a, s);
 }
 
 }  // namespace wave48

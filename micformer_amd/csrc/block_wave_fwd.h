@@ -40,22 +40,12 @@ __device__ __forceinline__ void stage_weights(char* lds, const micf_block_fwd_gr
   const uint16_t* wq = static_cast<const uint16_t*>(g.wq), *wkv = static_cast<const uint16_t*>(g.wkv), *wp = static_cast<const uint16_t*>(g.wp),
                  *w1 = static_cast<const uint16_t*>(g.w1), *w2 = static_cast<const uint16_t*>(g.w2);
   const int tid = threadIdx.x;
-  for (int s = tid; s < 9 * 64; s += NTHR) {
-    const int j = s >> 6, li = s & 15, lr = (s >> 4) & 3;
-    const uint16_t* W = j < 3 ? wq : wkv;
-    const int row = 16 * (j < 3 ? j : j - 3) + li;
-    *reinterpret_cast<u32x4v*>(lds + kQ32 + s * 16) = *reinterpret_cast<const u32x4v*>(W + k16(row, 8 * lr, 3));
-    *reinterpret_cast<u32x2v*>(lds + kQ16 + s * 8) = *reinterpret_cast<const u32x2v*>(W + k16(row, 32 + 4 * lr, 3));
-  }
+  stage_qkv_fwd(lds, kQ32, kQ16, wq, wkv, tid, NTHR);      // (block_wave.h: shared with the backward, which rebuilds q / k / v and h)
   for (int s = tid; s < 9 * 64; s += NTHR) {
     const int f = s >> 6, j = f / 3, h = f - 3 * j, li = s & 15, lr = (s >> 4) & 3;
     *reinterpret_cast<u32x2v*>(lds + kP16 + s * 8) = *reinterpret_cast<const u32x2v*>(wp + k16(row_p48(j, li), 16 * h + 4 * lr, 3));
   }
-  for (int s = tid; s < 12 * 64; s += NTHR) {
-    const int j = s >> 6, li = s & 15, lr = (s >> 4) & 3, row = row_p192(j, li);
-    *reinterpret_cast<u32x4v*>(lds + kF32 + s * 16) = *reinterpret_cast<const u32x4v*>(w1 + k16(row, 8 * lr, 3));
-    *reinterpret_cast<u32x2v*>(lds + kF16 + s * 8) = *reinterpret_cast<const u32x2v*>(w1 + k16(row, 32 + 4 * lr, 3));
-  }
+  stage_fc1_fwd(lds, kF32, kF16, w1, tid, NTHR);
   for (int s = tid; s < 18 * 64; s += NTHR) {
     const int f = s >> 6, j = f / 6, kc = f - 6 * j, li = s & 15, lr = (s >> 4) & 3;
     *reinterpret_cast<u32x4v*>(lds + kG32 + s * 16) = *reinterpret_cast<const u32x4v*>(w2 + k16(row_p48(j, li), 32 * kc + 8 * lr, 12));
@@ -235,7 +225,7 @@ __global__ void __launch_bounds__(NTHR) __attribute__((amdgpu_waves_per_eu(4, 4)
           }
         }
         const bf16x4_t kf = pack4q(qkv[1]);
-        if (live) {
+        if (live && g.q) {                               // (workgroup-uniform; NULL with kv and h: the backward rebuilds them from xn / kvs16)
           st2u(qo + 16 * h, pack4q(qkv[0]));
           st2u(ko + 16 * h, kf);
           st2u(ko + C + 16 * h, pack4q(qkv[2]));

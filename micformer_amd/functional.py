@@ -1062,12 +1062,24 @@ def _ln_partials(side, part, tiles, C, dg, db):
 FUSE_NEXT_LN = True
 
 
+# The wave-private kernels of the C = 48 stages rebuild q, k | v and the fc1 pre-activation in the backward launch instead of storing
+# them (ops.block_rebuilds; bit-identical results, 14 of the forward's ~45 bytes per element of T * C less).  True = all three,
+# "h" = the pre-activation only, False = everything stored (MICF_BLOCK_REBUILD=h / 0: measurement switch, results are the same bits).
+BLOCK_REBUILD = {"0": False, "h": "h"}.get(_os.environ.get("MICF_BLOCK_REBUILD", ""), True)
+
+
+def _rebuild(dims, C, heads, P):
+    return BLOCK_REBUILD if BLOCK_REBUILD and ops.block_rebuilds(dims, C, heads, P["mlp.fc1.weight"].shape[0]) else False
+
+
 def _self_fwd_fused(xs, Ps, scales, dims, heads, eps, save=True, next_ln=None):
     """xs: 1 or 2 [T, C] inputs (the two modalities); one launch.  Returns the per-group saved dicts (save=False: 'y' only).
     next_ln: [(gamma, beta)] per group -> every dict also has "nln" = (LayerNorm(y), mean, rstd); the launch clears `hid` where
     the offset convolution accumulates into it (returned as the second value then)."""
     C = xs[0].shape[1]
     groups = [{"x": x, "kvsrc": None, "P": P, "attn": "self_attn", "s1": s[0], "s2": s[1]} for x, P, s in zip(xs, Ps, scales)]
+    for gd in groups:
+        gd["rebuild"] = _rebuild(dims, C, heads, Ps[0])
     if next_ln is None:
         return ops.block_fwd(groups, dims, C, heads, eps, (C // heads) ** -0.5, save=save)
     hid = None
@@ -1094,7 +1106,7 @@ def lazy_ln_pending():
 def _self_bwd_fused(dys, xs, svs, Ps, Gs, scales, dims, heads, sides):
     C = xs[0].shape[1]
     rps = dims[1] * dims[2] * dims[3]
-    groups = [{"dy": dy, "x": x, "x1": sv["x1"], "stats": sv["stats"], "q": sv["q"], "kv": sv["kv"], "h": sv["h"], "xn2": sv["xn2"], "P": P,
+    groups = [{"dy": dy, "x": x, "x1": sv["x1"], "stats": sv["stats"], "q": sv["q"], "kv": sv["kv"], "h": sv["h"], "xn2": sv["xn2"], "xn": sv["xn"], "P": P,
                "attn": "self_attn", "s1": s[0], "s2": s[1], "cross": False} for dy, x, sv, P, s in zip(dys, xs, svs, Ps, scales)]
     pres = [CTX.lazy_ln.pop(dy.data_ptr(), None) for dy in dys]
     for gd, pre in zip(groups, pres):
@@ -1280,7 +1292,7 @@ class CrossPairFn(torch.autograd.Function):
             heads_ = [_cross_head_fwd(xs[i], xs[1 - i], Ps[i], dims, eps) for i in (0, 1)]
         scales = [(sa1, sa2), (sb1, sb2)]
         groups = [{"x": xs[i], "kvsrc": heads_[i][5], "P": Ps[i], "attn": "cross_attn", "s1": scales[i][0], "s2": scales[i][1],
-                   "want_xn": False} for i in (0, 1)]
+                   "want_xn": False, "rebuild": _rebuild(dims, C, heads, Ps[0])} for i in (0, 1)]
         if fuse_sampler:
             for i in (0, 1):
                 groups[i].update(kvsrc=None, hid=heads_[i][3], samp_src=xs[1 - i])
@@ -1318,8 +1330,8 @@ class CrossPairFn(torch.autograd.Function):
         rps = dims[1] * dims[2] * dims[3]
         dys = [_c(dy).reshape(-1, C), _c(dya).reshape(-1, C)]
         groups = [{"dy": dys[i], "x": None, "x1": svs[i]["x1"], "stats": svs[i]["stats"], "q": svs[i]["q"], "kv": svs[i]["kv"],
-                   "h": svs[i]["h"], "xn2": svs[i]["xn2"], "P": Ps[i], "attn": "cross_attn", "s1": scales[i][0], "s2": scales[i][1], "cross": True,
-                   "want_copy": True} for i in (0, 1)]
+                   "h": svs[i]["h"], "xn2": svs[i]["xn2"], "xn": svs[i]["xn"], "kvs16": svs[i]["kvs16"], "P": Ps[i], "attn": "cross_attn",
+                   "s1": scales[i][0], "s2": scales[i][1], "cross": True, "want_copy": True} for i in (0, 1)]
         bos = ops.block_bwd(groups, dims, C, heads, (C // heads) ** -0.5)
         acc = [bos[0]["dx1_copy"], bos[1]["dx1_copy"]]       # acc[i] becomes d(input i): starts as dx1 of block i
         for i in (0, 1):

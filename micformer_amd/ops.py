@@ -1122,7 +1122,20 @@ def block_recomputes_h(C, heads):
     return bool(_lib.lib.micf_block_recomputes_h(C, heads))
 
 
-def block_fwd(groups, dims, C, heads, eps, scale, persist_probe=None, save=True):
+def block_rebuilds(dims, C, heads, hidden):
+    """True when the fused block launches of this shape take the wave-private kernels in the current arithmetic mode, whose
+    backward rebuilds q, k | v and the fc1 pre-activation in registers (block_fwd(..., rebuild=True) then stores none of them):
+    the library's own condition (csrc/block_fwd.hip / block_bwd.hip: C = 48, head_dim 16, bf16 mode without the fp8 attention,
+    hook "block_wave" on, no probe flag, 32-bit offsets)."""
+    B, D, H, W = dims
+    T = B * D * H * W
+    return (_lib.get_option("block_wave") != 0 and C == 48 and C % heads == 0 and C // heads == 16
+            and _dt() == 1 and _dt_attn() == 1 and not (_lib.get_option("block_debug") & ~17)
+            and block_tile_tokens(dims, C, heads, hidden, backward=True) == 32
+            and T * C * 4 < (1 << 32) and T * hidden * 2 < (1 << 31))
+
+
+def block_fwd(groups, dims, C, heads, eps, scale, persist_probe=None, save=True, rebuild=False):
     """groups: 1 or 2 dicts {x [T,C], kvsrc [T,C] | None, P {state_dict-style name: tensor}, attn 'self_attn' | 'cross_attn',
     s1, s2 [B] | None, want_xn bool}.  ONE launch.  Returns per group a dict of the tensors saved for backward (+ 'y').
     A group may carry "next_ln": (gamma, beta, zero16 | None) -- the LayerNorm the NEXT block applies to this block's output (a cross
@@ -1130,7 +1143,11 @@ def block_fwd(groups, dims, C, heads, eps, scale, persist_probe=None, save=True)
     zero16: a [T, 16] fp32 tensor the launch clears.
     persist_probe: (repeats, int32[2] device tensor) -- the measurement probe micf_block_fwd_persistent_probe instead.
     save=False (no backward will follow): the inference form where the kernels have one (block_fuses_sampler shapes: everything but
-    the few-token decomposition) -- only 'y' is written, every other entry of the returned dicts is None."""
+    the few-token decomposition) -- only 'y' is written, every other entry of the returned dicts is None.
+    rebuild=True (block_rebuilds shapes only; the library refuses it elsewhere): 'q', 'kv' and 'h' are None -- block_bwd rebuilds
+    them from 'xn' / 'kvs16' / 'xn2' (pass xn and kvs16 along with q = kv = h = None there); rebuild="h": only 'h' is None.  The
+    groups may ask for it themselves with a "rebuild" entry (all alike)."""
+    rebuild = rebuild or groups[0].get("rebuild", False)
     B, D, H, W = dims
     T = B * D * H * W
     hidden = groups[0]["P"]["mlp.fc1.weight"].shape[0]
@@ -1160,6 +1177,10 @@ def block_fwd(groups, dims, C, heads, eps, scale, persist_probe=None, save=True)
                  "kvs16": _new(x, T, C, dtype=sd) if (st16 and cross) else None,
                  "flow": _new(x, T, 3) if fused_sampler else None,
                  "xs32": _new(x, T, C) if (fused_sampler and not st16) else None}
+            if rebuild:
+                o["h"] = None
+                if rebuild != "h":
+                    o["q"] = o["kv"] = None
         it.x, it.kvsrc, it.s1, it.s2 = f32(x), f32(gd.get("kvsrc")), f32(gd.get("s1")), f32(gd.get("s2"))
         if fused_sampler:
             it.hid, it.samp_src = f32(gd["hid"]), f32(gd["samp_src"])
@@ -1196,6 +1217,7 @@ def block_fwd(groups, dims, C, heads, eps, scale, persist_probe=None, save=True)
 
 def block_bwd(groups, dims, C, heads, scale):
     """groups: 1 or 2 dicts {dy, x, x1, stats, q, kv, h, P, attn, s1, s2, cross bool, want_copy bool, want_ln1 bool}.  ONE launch.
+    h None: rebuilt from {xn2}; q and kv None too (block_rebuilds shapes): rebuilt from {xn, kvs16 (cross)}.
     Returns per group {dx, dxs | None, dx1, dh, dq, dkv, ln1_part | None, ln2_part, tiles, dx1_copy | None}."""
     B, D, H, W = dims
     T = B * D * H * W
@@ -1220,10 +1242,17 @@ def block_bwd(groups, dims, C, heads, scale):
         for k in ("dy", "x", "x1", "stats", "s1", "s2"):
             setattr(it, k, f32(gd.get(k)))
         h = gd.get("h")
-        if (h is not None and h.dtype != (torch.bfloat16 if _dt() else torch.float32)) or gd["q"].dtype != sd or gd["kv"].dtype != sd \
-                or (h is None and gd["xn2"].dtype != sd):
+        reads = [gd[k] for k in ("q", "kv") if gd[k] is not None] + ([gd["xn2"]] if h is None else [])
+        if gd["q"] is None:                             # rebuilt: the bf16 rows the forward's products read
+            reads += [gd["xn"]] + ([gd["kvs16"]] if cross else [])
+        if (h is not None and h.dtype != (torch.bfloat16 if _dt() else torch.float32)) or any(t.dtype != sd for t in reads):
             raise _lib.MicfError("block_bwd: the saved tensors were written in another arithmetic mode")
         it.h, it.q, it.kv = ptr(h), ptr(gd["q"]), ptr(gd["kv"])
+        if gd["q"] is None:                             # ... with the FORWARD orientation of the q | kv weights and their biases
+            wf = block_weights(P, a, backward=False, only=("wq", "wkv"))
+            keep.append(wf)
+            it.xn, it.kvs16, it.wq, it.wkv = ptr(gd["xn"]), ptr(gd["kvs16"]) if cross else None, ptr(wf["wq"]), ptr(wf["wkv"])
+            it.bq, it.bkv = f32(P[f"{a}.q.bias"]), f32(P[f"{a}.kv.bias"])
         pre = gd.get("pre")
         if pre is not None:                             # the producing LayerNorm backward as the kernel's prologue (bf16 storage, self)
             if not st16 or cross:
@@ -1245,7 +1274,7 @@ def block_bwd(groups, dims, C, heads, scale):
         for k, v in o.items():
             setattr(it, k, ptr(v))
         # bytes the launch moves: read dy, x1, q, kv, h [+ x: self]; write everything in `o`; the weights once
-        nb += 4 * T * C * (2 if cross else 3) + sum(gd[k].numel() * gd[k].element_size() for k in ("q", "kv", "h" if h is not None else "xn2")) \
+        nb += 4 * T * C * (2 if cross else 3) + sum(t.numel() * t.element_size() for t in reads + ([h] if h is not None else [])) \
             + sum(v.numel() * v.element_size() for v in o.values() if v is not None) + 12 * C * C * wt.element_size()
         o["tiles"] = tiles
         outs.append(o)
