@@ -10,6 +10,8 @@
 What is computed, per sample (each array is resized independently from its own shape):
   * min-max normalisation of each image volume over the whole volume, (x - min) / (max - min), with one IEEE float32 divide per
     element.  A constant volume gives NaN everywhere, as the reference does.  NaN in the input is out of scope.
+    `normalisation=` chooses "zscore" or "percentile" instead, for both channels or per channel (micformer_amd/normalise.py has
+    the rules; those calls run on csrc/volume_normalise.hip, the default runs exactly as before).
   * trilinear resize (align_corners=False) of the normalised volumes to `size`, float16, channel 0 = CT, channel 1 = MR.
   * nearest resize of the CT label + lookup in `label_values` -> class map: 0 where the label is 0, k where it equals
     label_values[k - 1], 255 elsewhere.  (The reference's MR label planes are dropped by its `label[:8]` and are not computed.)
@@ -27,7 +29,7 @@ import ctypes
 
 import torch
 
-from . import _args, _lib
+from . import _args, _lib, normalise
 
 MMWHS_LABEL_VALUES = (205, 420, 500, 550, 600, 820, 850)          # MMWHS.py:289; class k = label_values[k - 1], class 0 = label 0
 MAX_LABEL_VALUES = 254
@@ -81,12 +83,17 @@ def _label_values(label_values):
     return _args.int32_array(vals), len(vals)
 
 
-def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, out=None):
+def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, out=None, normalisation="minmax",
+               percentiles=(1, 99), return_stats=False):
     """samples: sequence of (ct, mr, ct_label | None), every array an own-shaped (d, h, w) CUDA tensor (images int16 / float32,
     labels int16 / int32), labels present for all samples or for none.  out: optional preallocated (image, label_map,
-    crop_indexes) to write into.  -> (image fp16 [B, 2, D, H, W], label_map uint8 [B, D, H, W] | None, crop_indexes int32 [B, 3, 2])."""
+    crop_indexes) to write into.  normalisation: "minmax" | "zscore" | "percentile", or a (ct, mr) pair of them; percentiles:
+    (low, high) of the "percentile" mode.  return_stats=True appends the float64 [B, 2, 2] statistics of the normalisers.
+    -> (image fp16 [B, 2, D, H, W], label_map uint8 [B, D, H, W] | None, crop_indexes int32 [B, 3, 2])[, stats]."""
     D, H, W = _args.triple(size, "size")
     vals, nvals = _label_values(label_values)
+    ct_mode, mr_mode = normalise.modes(normalisation)
+    p_low, p_high = normalise.percentile_pair(percentiles)
     samples = list(samples)
     if not samples:
         raise ValueError("load_batch needs at least one sample")
@@ -126,17 +133,29 @@ def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, o
             raise ValueError("out label_map must be given exactly when the samples have labels")
         label_map = _args.out_tensor(out[1], "out label_map", (B, D, H, W), torch.uint8, device) if has_label else None
         crop = _args.out_tensor(out[2], "out crop_indexes", (B, 3, 2), torch.int32, device)
-    nbytes = _lib.query_bytes("micf_volume_loader_workspace", B)
+    if (ct_mode, mr_mode) == (normalise.MINMAX, normalise.MINMAX) and not return_stats:
+        nbytes = _lib.query_bytes("micf_volume_loader_workspace", B)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.call_on(device, "micf_volume_loader", ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals,
+                     ws.data_ptr(), nbytes, image.data_ptr(), None if label_map is None else label_map.data_ptr(), crop.data_ptr())
+        return image, label_map, crop
+    stats = torch.empty((B, 2, 2), dtype=torch.float64, device=device) if return_stats else None
+    nbytes = _lib.query_bytes("micf_volume_loader_norm_workspace", B)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    _lib.call_on(device, "micf_volume_loader", ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals, ws.data_ptr(),
-                 nbytes, image.data_ptr(), None if label_map is None else label_map.data_ptr(), crop.data_ptr())
-    return image, label_map, crop
+    _lib.call_on(device, "micf_volume_loader_norm", ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals, ct_mode,
+                 mr_mode, p_low, p_high, ws.data_ptr(), nbytes, image.data_ptr(),
+                 None if label_map is None else label_map.data_ptr(), crop.data_ptr(), None if stats is None else stats.data_ptr())
+    return (image, label_map, crop, stats) if return_stats else (image, label_map, crop)
 
 
-def load_pair(ct, mr, ct_label=None, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES):
-    """One sample: -> (image fp16 [2, D, H, W], label_map uint8 [D, H, W] | None, crop_indexes int32 [3, 2])."""
-    image, label_map, crop = load_batch([(ct, mr, ct_label)], size=size, label_values=label_values)
-    return image[0], None if label_map is None else label_map[0], crop[0]
+def load_pair(ct, mr, ct_label=None, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, normalisation="minmax",
+              percentiles=(1, 99), return_stats=False):
+    """One sample: -> (image fp16 [2, D, H, W], label_map uint8 [D, H, W] | None, crop_indexes int32 [3, 2])[, stats float64
+    [2, 2]]."""
+    res = load_batch([(ct, mr, ct_label)], size=size, label_values=label_values, normalisation=normalisation,
+                     percentiles=percentiles, return_stats=return_stats)
+    one = (res[0][0], None if res[1] is None else res[1][0], res[2][0])
+    return one + (res[3][0],) if return_stats else one
 
 
 __all__ = ["load_pair", "load_batch", "MMWHS_LABEL_VALUES", "SIGNATURES"]

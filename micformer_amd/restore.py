@@ -125,13 +125,14 @@ def restore_labels(logits, shape, label_values=MMWHS_LABEL_VALUES, probabilities
                          out=None if out is None else [out])[0]
 
 
-def segment_pair(model, ct, mr, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, probabilities=False, keep_largest=False):
+def segment_pair(model, ct, mr, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, probabilities=False, keep_largest=False,
+                 normalisation="minmax", percentiles=(1, 99)):
     """Raw CT / MR volumes of one sample (own-shaped (d, h, w) CUDA tensors, int16 / float32) -> the label volume of the CT's own
     shape: loader.load_pair -> data.prepare_raw_batch(image, None, None) (the validation transform) -> model under no_grad ->
     restore_labels at ct.shape.  keep_largest=True: the restored volume then goes through postprocess.keep_largest_components in
-    place (of every class only its largest 26-connected component stays)."""
+    place (of every class only its largest 26-connected component stays).  normalisation / percentiles: loader.load_pair's."""
     from . import data, loader
-    image, _, _ = loader.load_pair(ct, mr, None, size=size)
+    image, _, _ = loader.load_pair(ct, mr, None, size=size, normalisation=normalisation, percentiles=percentiles)
     x, _ = data.prepare_raw_batch(image.unsqueeze(0), None, None)
     with torch.no_grad():
         logits = model(x)

@@ -1,13 +1,17 @@
 """Time micformer_amd.loader.load_batch on a full-size MM-WHS-like pair (363x512x512 int16 CT + float32 MR + int16 CT label -> 128^3);
 one JSON line per batch size.
 
-    python tools/bench_loader.py [--batches 1,4] [--min-seconds 0.5] [--no-cpu]
+    python tools/bench_loader.py [--batches 1,4] [--min-seconds 0.5] [--no-cpu] [--normalisation minmax|zscore|percentile|CT,MR]
 
 ms_per_call: device events around >= min-seconds of calls after warm-up (the whole call: workspace zeroing, min/max, resize + label + crop,
 crop finish).  minmax_ms: the same call with a 1x1x1 target, i.e. the full read of the raw image volumes plus launch overheads;
 minmax_GBps: the raw image bytes of the batch (the bytes that pass must read) over that time.  resize_ms: the difference of the two.
 Per-kernel times proper come from a kernel trace of this script (loader_minmax_kernel / loader_resize_kernel / loader_crop_kernel).
 cpu_s: the CPU referee (tests/loader_ref.py: numpy + F.interpolate, the reference's own operators) for ONE sample on this host.
+--normalisation other than the default "minmax" times the same call through micf_volume_loader_norm (csrc/volume_normalise.hip):
+the 1x1x1-target call is then the statistics passes of that mode (moments; histogram + scan per digit), reported as stats_ms /
+stats_GBps against the same raw image bytes read ONCE (the percentile mode reads them two or three times), and cpu_s is
+tests/normalise_ref.py.
 """
 import argparse
 import json
@@ -59,7 +63,10 @@ def main():
     ap.add_argument("--batches", default="1,4")
     ap.add_argument("--min-seconds", type=float, default=0.5)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--normalisation", default="minmax", help="one mode for both channels, or CT,MR")
     a = ap.parse_args()
+    norm = tuple(a.normalisation.split(",")) if "," in a.normalisation else a.normalisation
+    default = norm == "minmax"
     if not torch.cuda.is_available():
         raise SystemExit("bench_loader.py needs the GPU")
     import loader_ref
@@ -69,7 +76,11 @@ def main():
     cpu = None
     if not a.no_cpu:
         t0 = time.perf_counter()
-        loader_ref.load_pair(*host, size=SIZE)
+        if default:
+            loader_ref.load_pair(*host, size=SIZE)
+        else:
+            import normalise_ref
+            normalise_ref.load_pair(*host, size=SIZE, normalisation=norm)
         cpu = time.perf_counter() - t0
     first = tuple(torch.from_numpy(x).cuda() for x in host)
     samples = [first] + [tuple(t.clone() for t in first) for _ in range(max(batches) - 1)]      # distinct buffers per sample
@@ -80,14 +91,19 @@ def main():
                torch.empty((B,) + SIZE, dtype=torch.uint8, device="cuda"), torch.empty((B, 3, 2), dtype=torch.int32, device="cuda"))
         tiny = (torch.empty((B, 2, 1, 1, 1), dtype=torch.float16, device="cuda"),
                 torch.empty((B, 1, 1, 1), dtype=torch.uint8, device="cuda"), torch.empty((B, 3, 2), dtype=torch.int32, device="cuda"))
-        total, calls = timed(lambda: loader.load_batch(dev, size=SIZE, out=out), a.min_seconds)
-        mm, _ = timed(lambda: loader.load_batch(dev, size=(1, 1, 1), out=tiny), a.min_seconds)
-        print(json.dumps({"case": "x".join(map(str, SHAPE)) + " -> " + "x".join(map(str, SIZE)), "B": B,
-                          "ms_per_call": round(total, 4), "ms_per_pair": round(total / B, 4), "calls": calls,
-                          "minmax_ms": round(mm, 4), "minmax_GBps": round(B * raw_bytes / mm / 1e6, 1),
-                          "resize_ms": round(total - mm, 4), "raw_image_bytes_per_pair": raw_bytes,
-                          "cpu_s": None if cpu is None else round(cpu, 3),
-                          "crop_indexes": out[2][0].cpu().tolist()}), flush=True)
+        kw = {} if default else {"normalisation": norm}
+        total, calls = timed(lambda: loader.load_batch(dev, size=SIZE, out=out, **kw), a.min_seconds)
+        mm, _ = timed(lambda: loader.load_batch(dev, size=(1, 1, 1), out=tiny, **kw), a.min_seconds)
+        first_pass = "minmax" if default else "stats"
+        row = {"case": "x".join(map(str, SHAPE)) + " -> " + "x".join(map(str, SIZE)), "B": B,
+               "ms_per_call": round(total, 4), "ms_per_pair": round(total / B, 4), "calls": calls,
+               first_pass + "_ms": round(mm, 4), first_pass + "_GBps": round(B * raw_bytes / mm / 1e6, 1),
+               "resize_ms": round(total - mm, 4), "raw_image_bytes_per_pair": raw_bytes,
+               "cpu_s": None if cpu is None else round(cpu, 3),
+               "crop_indexes": out[2][0].cpu().tolist()}
+        if not default:
+            row["normalisation"] = a.normalisation
+        print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":
