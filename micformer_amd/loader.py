@@ -7,6 +7,11 @@
     image, label_map, crop = loader.load_batch([(ct, mr, lab), ...])        # fp16 [B,2,128,128,128], uint8 [B,128,128,128], int32 [B,3,2]
     x, y = data.prepare_raw_batch(image, label_map, params)                 # the device-side tail; y feeds MDiceLoss as it is
 
+Geometric augmentation rides in the same pass (micformer_amd/affine.py has the rules; those calls run on csrc/volume_affine.hip):
+    theta = affine.draw_affine(len(samples), generator=g, device="cuda")    # [B, 3, 4]: rotate / zoom / translate per sample
+    image, label_map, crop = loader.load_batch(samples, affine=theta, padding_mode="border")
+    theta.copy_(affine.draw_affine(len(samples), generator=g))              # a graph captured with out= reads the new draws
+
 What is computed, per sample (each array is resized independently from its own shape):
   * min-max normalisation of each image volume over the whole volume, (x - min) / (max - min), with one IEEE float32 divide per
     element.  A constant volume gives NaN everywhere, as the reference does.  NaN in the input is out of scope.
@@ -29,7 +34,7 @@ import ctypes
 
 import torch
 
-from . import _args, _lib, normalise
+from . import _args, _lib, affine as _affine, normalise
 
 MMWHS_LABEL_VALUES = (205, 420, 500, 550, 600, 820, 850)          # MMWHS.py:289; class k = label_values[k - 1], class 0 = label 0
 MAX_LABEL_VALUES = 254
@@ -84,20 +89,27 @@ def _label_values(label_values):
 
 
 def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, out=None, normalisation="minmax",
-               percentiles=(1, 99), return_stats=False):
+               percentiles=(1, 99), return_stats=False, affine=None, padding_mode="zeros"):
     """samples: sequence of (ct, mr, ct_label | None), every array an own-shaped (d, h, w) CUDA tensor (images int16 / float32,
     labels int16 / int32), labels present for all samples or for none.  out: optional preallocated (image, label_map,
     crop_indexes) to write into.  normalisation: "minmax" | "zscore" | "percentile", or a (ct, mr) pair of them; percentiles:
     (low, high) of the "percentile" mode.  return_stats=True appends the float64 [B, 2, 2] statistics of the normalisers.
+    affine: optional float32 CUDA [B, 3, 4] (one map per sample) or [B, 2, 3, 4] (index 0 CT and label, index 1 MR), the
+    F.affine_grid theta the resample reads on the device; padding_mode: "zeros" | "border", read only with `affine`.
     -> (image fp16 [B, 2, D, H, W], label_map uint8 [B, D, H, W] | None, crop_indexes int32 [B, 3, 2])[, stats]."""
     D, H, W = _args.triple(size, "size")
     vals, nvals = _label_values(label_values)
     ct_mode, mr_mode = normalise.modes(normalisation)
     p_low, p_high = normalise.percentile_pair(percentiles)
+    if affine is not None:
+        _affine.typed(affine)
+        pad = _affine.padding(padding_mode)
     samples = list(samples)
     if not samples:
         raise ValueError("load_batch needs at least one sample")
     B = len(samples)
+    if affine is not None:
+        per_modality = _affine.maps(affine, B)
     items = (LoaderSample * B)()
     device, has_label = None, None
     for b, smp in enumerate(samples):
@@ -133,6 +145,17 @@ def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, o
             raise ValueError("out label_map must be given exactly when the samples have labels")
         label_map = _args.out_tensor(out[1], "out label_map", (B, D, H, W), torch.uint8, device) if has_label else None
         crop = _args.out_tensor(out[2], "out crop_indexes", (B, 3, 2), torch.int32, device)
+    if affine is not None:
+        if affine.device != device:
+            raise ValueError(f"affine is on {affine.device}, the batch on {device}")
+        stats = torch.empty((B, 2, 2), dtype=torch.float64, device=device) if return_stats else None
+        nbytes = _lib.query_bytes("micf_volume_loader_affine_workspace", B)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.call_on(device, "micf_volume_loader_affine", ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals,
+                     ct_mode, mr_mode, p_low, p_high, ws.data_ptr(), nbytes, image.data_ptr(),
+                     None if label_map is None else label_map.data_ptr(), crop.data_ptr(),
+                     None if stats is None else stats.data_ptr(), affine.data_ptr(), per_modality, pad)
+        return (image, label_map, crop, stats) if return_stats else (image, label_map, crop)
     if (ct_mode, mr_mode) == (normalise.MINMAX, normalise.MINMAX) and not return_stats:
         nbytes = _lib.query_bytes("micf_volume_loader_workspace", B)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -149,11 +172,18 @@ def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, o
 
 
 def load_pair(ct, mr, ct_label=None, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, normalisation="minmax",
-              percentiles=(1, 99), return_stats=False):
+              percentiles=(1, 99), return_stats=False, affine=None, padding_mode="zeros"):
     """One sample: -> (image fp16 [2, D, H, W], label_map uint8 [D, H, W] | None, crop_indexes int32 [3, 2])[, stats float64
-    [2, 2]]."""
+    [2, 2]].  affine: [3, 4] or [2, 3, 4]."""
+    if affine is not None:
+        _affine.typed(affine)
+        if not isinstance(padding_mode, str):
+            _affine.padding(padding_mode)                            # (its TypeError before the first ValueError)
+        if affine.dim() not in (2, 3):
+            raise ValueError(f"affine of load_pair must have shape [3, 4] or [2, 3, 4], got {list(affine.shape)}")
+        affine = affine.unsqueeze(0)                                 # (a view: the kernels read the caller's tensor)
     res = load_batch([(ct, mr, ct_label)], size=size, label_values=label_values, normalisation=normalisation,
-                     percentiles=percentiles, return_stats=return_stats)
+                     percentiles=percentiles, return_stats=return_stats, affine=affine, padding_mode=padding_mode)
     one = (res[0][0], None if res[1] is None else res[1][0], res[2][0])
     return one + (res[3][0],) if return_stats else one
 

@@ -2,6 +2,7 @@
 one JSON line per batch size.
 
     python tools/bench_loader.py [--batches 1,4] [--min-seconds 0.5] [--no-cpu] [--normalisation minmax|zscore|percentile|CT,MR]
+                                 [--affine [--padding-mode zeros|border]]
 
 ms_per_call: device events around >= min-seconds of calls after warm-up (the whole call: workspace zeroing, min/max, resize + label + crop,
 crop finish).  minmax_ms: the same call with a 1x1x1 target, i.e. the full read of the raw image volumes plus launch overheads;
@@ -12,6 +13,11 @@ cpu_s: the CPU referee (tests/loader_ref.py: numpy + F.interpolate, the referenc
 the 1x1x1-target call is then the statistics passes of that mode (moments; histogram + scan per digit), reported as stats_ms /
 stats_GBps against the same raw image bytes read ONCE (the percentile mode reads them two or three times), and cpu_s is
 tests/normalise_ref.py.
+--affine times the same call with a drawn map per sample (affine.draw_affine, csrc/volume_affine.hip) next to the call without one:
+affine_ms_per_call against plain_ms_per_call, affine_stats_ms (the 1x1x1-target call: the statistics passes, which do not depend on
+the map) and affine_resample_ms (the difference), plus grid_sample_ms: F.affine_grid + F.grid_sample (bilinear) on the already
+loaded float16 image of the batch with the same maps, the second resample a user would run today (the label would need a third).
+There is no bar; the raw-volume statistics pass should still dominate.
 """
 import argparse
 import json
@@ -64,6 +70,8 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.5)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--normalisation", default="minmax", help="one mode for both channels, or CT,MR")
+    ap.add_argument("--affine", action="store_true", help="also time the call with a drawn affine map per sample")
+    ap.add_argument("--padding-mode", default="zeros", choices=["zeros", "border"])
     a = ap.parse_args()
     norm = tuple(a.normalisation.split(",")) if "," in a.normalisation else a.normalisation
     default = norm == "minmax"
@@ -103,6 +111,19 @@ def main():
                "crop_indexes": out[2][0].cpu().tolist()}
         if not default:
             row["normalisation"] = a.normalisation
+        if a.affine:
+            import torch.nn.functional as F
+            from micformer_amd import affine
+            theta = affine.draw_affine(B, size=SIZE, generator=torch.Generator().manual_seed(B), device="cuda")
+            akw = dict(kw, affine=theta, padding_mode=a.padding_mode)
+            at, _ = timed(lambda: loader.load_batch(dev, size=SIZE, out=out, **akw), a.min_seconds)
+            ast, _ = timed(lambda: loader.load_batch(dev, size=(1, 1, 1), out=tiny, **akw), a.min_seconds)
+            image = out[0].clone()
+            gs, _ = timed(lambda: F.grid_sample(image, F.affine_grid(theta, image.shape, align_corners=False).to(image.dtype),
+                                                mode="bilinear", padding_mode=a.padding_mode, align_corners=False), a.min_seconds)
+            row.update({"padding_mode": a.padding_mode, "plain_ms_per_call": row["ms_per_call"], "affine_ms_per_call": round(at, 4),
+                        "affine_stats_ms": round(ast, 4), "affine_resample_ms": round(at - ast, 4),
+                        "affine_minus_plain_ms": round(at - total, 4), "grid_sample_ms": round(gs, 4)})
         print(json.dumps(row), flush=True)
 
 
