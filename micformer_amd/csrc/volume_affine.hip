@@ -1,8 +1,9 @@
 // volume_affine.hip -- the volume loader with an affine map in its resample pass (include/micformer_affine.h): every output voxel
 // reads the raw CT / MR / label arrays at theta . (its normalised coordinate), F.affine_grid + F.grid_sample(align_corners=False),
 // with the normalisation of volume_normalise.hip applied to each tap.  The coordinate, clamp and index arithmetic is
-// affine_coords.h's (host-callable); the statistics passes, the records and the per-channel normaliser are
-// volume_normalise_stats.h's, shared with volume_normalise.hip.
+// affine_coords.h's (host-callable); everything else but the resample kernel -- the statistics passes, the per-channel normaliser,
+// the crop extents and label lookup, the host sequence (run_stats_loader) -- is volume_normalise_stats.h's and
+// volume_loader_common.h's.
 //
 // Launch plan of micf_volume_loader_affine (batched over the samples, 8 per launch, no host round trip):
 //   0 zero, 1-4 the statistics passes the two modes need and their finish: volume_normalise.hip's plan, unchanged (the statistics
@@ -10,9 +11,9 @@
 //   5 resample   resize_kernel's shape: grid (blocks, samples of the chunk), one thread per output voxel, x fastest so the fp16 and
 //                uint8 stores coalesce; the sample's 12 or 24 floats of theta read once per block into LDS; per voxel one
 //                normalised coordinate, one source coordinate per map, and per array the three indices, the 8 taps normalised in
-//                registers (NormAny: every mode in one launch), the nearest label tap + value lookup; the crop extents reduced as
-//                in resize_kernel
-//   6 crop       extents -> crop_indexes
+//                registers (NormAny: every mode in one launch), the nearest label tap + value lookup; the crop extents reduced by
+//                resize_kernel's Extents
+//   6 crop       loader_crop_kernel on the records: extents -> crop_indexes
 // Everything that crosses threads is an integer count, sum or maximum, or is merged in a fixed order: bit-identical from run to run.
 #include "volume_normalise_stats.h"
 #include "affine_coords.h"
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(kThreads) void affine_resample_kernel(ResizeArgs a,
   const float* tc = s_theta;
   const float* tm = s_theta + 12;
   const bool bd = border != 0;
-  uint32_t ez = 0, ey = 0, ex = 0, fz = 0, fy = 0, fx = 0;
+  Extents ext;
   for (int v = blockIdx.x * kThreads + tid; v < V; v += gridDim.x * kThreads) {
     const int x = v % W, t = v / W, y = t % H, z = t / H;
     const float nx = micf_affine::norm_coord(x, W), ny = micf_affine::norm_coord(y, H), nz = micf_affine::norm_coord(z, D);
@@ -91,11 +92,7 @@ __global__ __launch_bounds__(kThreads) void affine_resample_kernel(ResizeArgs a,
     }
     img[v] = __float2half_rn(c0);
     img[(size_t)V + v] = __float2half_rn(c1);
-    if (c0 != 0.0f || c1 != 0.0f) {                              // (true for NaN, as numpy's `!= 0`)
-      ez = max(ez, (uint32_t)(z + 1)); fz = max(fz, (uint32_t)(D - z));
-      ey = max(ey, (uint32_t)(y + 1)); fy = max(fy, (uint32_t)(H - y));
-      ex = max(ex, (uint32_t)(x + 1)); fx = max(fx, (uint32_t)(W - x));
-    }
+    if (c0 != 0.0f || c1 != 0.0f) ext.see(z, y, x, D, H, W);       // (true for NaN, as numpy's `!= 0`)
     if (label_map) {
       const Vol3& lv = sd.lab;
       int val = 0;                                               // outside the array, or a non-finite coordinate: raw label 0
@@ -104,31 +101,12 @@ __global__ __launch_bounds__(kThreads) void affine_resample_kernel(ResizeArgs a,
         bool inz, iny, inx;
         const int sz = micf_affine::nearest_tap(i.z, lv.d, bd, inz), sy = micf_affine::nearest_tap(i.y, lv.h, bd, iny),
                   sx = micf_affine::nearest_tap(i.x, lv.w, bd, inx);
-        if (inz && iny && inx) {
-          const int64_t off = ((int64_t)sz * lv.h + sy) * lv.w + sx;
-          val = lv.dtype == MICF_LOADER_I32 ? static_cast<const int32_t*>(lv.p)[off] : (int)static_cast<const int16_t*>(lv.p)[off];
-        }
+        if (inz && iny && inx) val = raw_label(lv, ((int64_t)sz * lv.h + sy) * lv.w + sx);
       }
-      int cls = val == 0 ? 0 : 255;
-      for (int k = 0; k < a.nvals; ++k) cls = val == a.vals[k] ? k + 1 : cls;
-      label_map[(size_t)blockIdx.y * V + v] = (uint8_t)cls;
+      label_map[(size_t)blockIdx.y * V + v] = (uint8_t)label_class(a, val);
     }
   }
-  ez = wave_umax(ez); ey = wave_umax(ey); ex = wave_umax(ex);
-  fz = wave_umax(fz); fy = wave_umax(fy); fx = wave_umax(fx);
-  if ((tid & 63) == 0) {
-    atomicMax(&s_ext[0], ez); atomicMax(&s_ext[1], ey); atomicMax(&s_ext[2], ex);
-    atomicMax(&s_ext[3], fz); atomicMax(&s_ext[4], fy); atomicMax(&s_ext[5], fx);
-  }
-  __syncthreads();
-  if (tid < 6 && s_ext[tid] != 0) atomicMax(rec->ext + tid, s_ext[tid]);
-}
-
-// ---- 6. crop_indexes --------------------------------------------------------------------------------------------------------------
-__global__ void affine_crop_kernel(const SampleRec* recs, int B, int D, int H, int W, int32_t* crop) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * 3) return;
-  crop_body(recs[i / 3].ext, i % 3, D, H, W, crop + i * 2);
+  ext.flush(s_ext, rec->ext);
 }
 
 }  // namespace
@@ -146,41 +124,18 @@ extern "C" int micf_volume_loader_affine(const micf_loader_sample* samples, int 
   if (!affine || (reinterpret_cast<uintptr_t>(affine) & 3)) return MICF_EINVAL;
   if (affine_per_modality != 0 && affine_per_modality != 1) return MICF_EINVAL;
   if (padding_mode != MICF_PAD_ZEROS && padding_mode != MICF_PAD_BORDER) return MICF_EINVAL;
-  if (!valid_mode(ct_mode) || !valid_mode(mr_mode)) return MICF_EINVAL;
-  if (!(0.0 <= p_low && p_low < p_high && p_high <= 100.0)) return MICF_EINVAL;      // (false for NaN)
-  if (reinterpret_cast<uintptr_t>(stats) & 7) return MICF_EINVAL;
-  const int rc = check_call(samples, B, D, H, W, label_values, num_label_values, workspace, workspace_bytes,
-                            B > 0 ? layout(B).total : 0, image, label_map, crop_indexes);
+  int rc = check_norm_args(ct_mode, mr_mode, p_low, p_high, stats);
+  if (rc != MICF_OK) return rc;
+  rc = check_call(samples, B, D, H, W, label_values, num_label_values, workspace, workspace_bytes, B > 0 ? layout(B).total : 0,
+                  image, label_map, crop_indexes);
   if (rc != MICF_OK) return rc;
 
   hipStream_t s = (hipStream_t)stream;
-  const Layout L = layout(B);
-  char* ws = static_cast<char*>(workspace);
-  uint32_t* words = reinterpret_cast<uint32_t*>(ws);
-  SampleRec* recs = reinterpret_cast<SampleRec*>(ws + L.recs);
-  uint32_t* hist = reinterpret_cast<uint32_t*>(ws + L.hist);
-  Mom* partials = reinterpret_cast<Mom*>(ws + L.partials);
-  const int64_t V = (int64_t)D * H * W;
-  const Modes md{{ct_mode, mr_mode}};
-  const int64_t zb = (L.zero_words + kThreads - 1) / kThreads;
-  hipLaunchKernelGGL(norm_zero_kernel, dim3((unsigned)(zb < 1024 ? zb : 1024)), dim3(kThreads), 0, s,
-                     reinterpret_cast<uint32_t*>(ws), L.zero_words);
-  ResizeArgs ra;
-  fill_label_values(ra, label_values, num_label_values);
-  const unsigned rblocks = resize_blocks(V);
   const int nth = affine_per_modality ? 24 : 12;
-  for (int b0 = 0; b0 < B; b0 += kChunk) {
-    const int nb = B - b0 < kChunk ? B - b0 : kChunk;
-    MinMaxArgs ma;
-    const unsigned blocks = pass_blocks(fill_chunk(samples, b0, nb, ma, ra));
-    SampleRec* rc0 = recs + b0;
-    launch_statistics(s, ma, md, nb, blocks, p_low, p_high, words + (size_t)b0 * kWsWords, rc0,
-                      hist + (size_t)b0 * 2 * kRanks * kBins, partials + (size_t)b0 * 2 * kMaxPartials,
-                      stats ? stats + (size_t)b0 * 4 : nullptr);
-    hipLaunchKernelGGL(affine_resample_kernel, dim3(rblocks, (unsigned)nb), dim3(kThreads), 0, s, ra, D, H, W, rc0,
-                       affine + (size_t)b0 * nth, affine_per_modality, padding_mode,
-                       static_cast<__half*>(image) + (size_t)b0 * 2 * V, label_map ? label_map + (size_t)b0 * V : nullptr);
-  }
-  hipLaunchKernelGGL(affine_crop_kernel, dim3((unsigned)((B * 3 + 63) / 64)), dim3(64), 0, s, recs, B, D, H, W, crop_indexes);
-  MICF_RETURN_LAUNCH();
+  return run_stats_loader(samples, B, D, H, W, label_values, num_label_values, Modes{{ct_mode, mr_mode}}, p_low, p_high, workspace,
+                          image, label_map, crop_indexes, stats, s, false,
+                          [&](const ResizeArgs& ra, const WsView& c, int b0, dim3 grid, __half* img0, uint8_t* lab0) {
+                            hipLaunchKernelGGL(affine_resample_kernel, grid, dim3(kThreads), 0, s, ra, D, H, W, c.recs,
+                                               affine + (size_t)b0 * nth, affine_per_modality, padding_mode, img0, lab0);
+                          });
 }

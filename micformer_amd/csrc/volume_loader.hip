@@ -3,41 +3,24 @@
 // MMWHS_noCrop_Augment.__getitem__ (MMWHS.py:308-405) and normalize (image_utils.py:48-55).
 //
 // Launch plan of micf_volume_loader (batched over the samples, 8 per launch, no host round trip):
-//   0 zero       the workspace words (all of them are running maxima that start at 0)
+//   0 zero       loader_zero_kernel: the workspace words (all of them are running maxima that start at 0)
 //   1 minmax     the one full read of every raw image volume: 128-bit loads, wave + block reduction, two integer atomicMax per block
 //                on order-preserving keys (max of key, max of ~key), so the result does not depend on arrival order
-//   2 resize     one thread per output voxel: 8 trilinear taps of CT and of MR read in the raw dtype and normalised in registers
-//                (one IEEE divide per tap, as the reference normalises before it resizes), fp16 stores; the nearest label gather +
-//                value lookup; the extents of the non-zero voxels reduced per block, six integer atomicMax per block
-//   3 finish     extents -> crop_indexes (max(0, min - 1), max + 1), (0, 0) where the image is all zero
+//   2 resize     resize_kernel<LoaderWords>, one thread per output voxel: 8 trilinear taps of CT and of MR read in the raw dtype and
+//                normalised in registers (one IEEE divide per tap, as the reference normalises before it resizes), fp16 stores; the
+//                nearest label gather + value lookup; the extents of the non-zero voxels reduced per block, six integer atomicMax
+//                per block
+//   3 finish     loader_crop_kernel: extents -> crop_indexes (max(0, min - 1), max + 1), (0, 0) where the image is all zero
 // Everything that crosses threads is an integer maximum: the outputs are bit-identical from run to run.
 #include "volume_loader_common.h"
 
-
-
 namespace {
-
-// ---- 0. the running maxima start at 0.  A kernel, not hipMemsetAsync: captured into a graph, the memset node of these few words left
-// stale words behind at the second replay on ROCm 7.2 (tests/test_gpu_loader.py::test_capture_and_replay_under_a_graph caught it).
-__global__ void loader_zero_kernel(uint32_t* ws, int words) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < words) ws[i] = 0;
-}
 
 // ---- 1. min / max of every raw image volume (minmax_body) ----------------------------------------------------------------------
 // grid (blocks, volumes).  keys: [sample][kWsWords] words, volume 2 s + c at words 2 c, 2 c + 1 of sample s.
 __global__ __launch_bounds__(kThreads) void loader_minmax_kernel(MinMaxArgs a, uint32_t* keys) {
   __shared__ uint32_t s_red[2 * kWaves];
   minmax_body(a.v[blockIdx.y], keys + (size_t)(blockIdx.y >> 1) * kWsWords + 2 * (blockIdx.y & 1), s_red);
-}
-
-// ---- 2. resize + label + crop extents: resize_kernel<LoaderWords> (volume_loader_common.h) ---------------------------------------
-
-// ---- 3. crop_indexes ----------------------------------------------------------------------------------------------------------
-__global__ void loader_crop_kernel(const uint32_t* ws, int B, int D, int H, int W, int32_t* crop) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * 3) return;
-  crop_body(ws + (size_t)(i / 3) * kWsWords + 4, i % 3, D, H, W, crop + i * 2);
 }
 
 }  // namespace
@@ -57,20 +40,16 @@ extern "C" int micf_volume_loader(const micf_loader_sample* samples, int B, int 
   hipStream_t s = (hipStream_t)stream;
   uint32_t* ws = static_cast<uint32_t*>(workspace);
   const int64_t V = (int64_t)D * H * W;
-  hipLaunchKernelGGL(loader_zero_kernel, dim3((unsigned)((B * kWsWords + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, ws,
-                     B * kWsWords);
+  launch_zero(s, ws, (int64_t)B * kWsWords);
+  MinMaxArgs ma;
   ResizeArgs ra;
   fill_label_values(ra, label_values, num_label_values);
-  const unsigned rblocks = resize_blocks(V);
-  for (int b0 = 0; b0 < B; b0 += kChunk) {
-    const int nb = B - b0 < kChunk ? B - b0 : kChunk;
-    MinMaxArgs ma;
-    const unsigned mblocks = pass_blocks(fill_chunk(samples, b0, nb, ma, ra));
+  for_each_chunk(samples, B, ma, ra, [&](int b0, int nb, unsigned mblocks) {
     uint32_t* wsc = ws + (size_t)b0 * kWsWords;
     hipLaunchKernelGGL(loader_minmax_kernel, dim3(mblocks, (unsigned)(2 * nb)), dim3(kThreads), 0, s, ma, wsc);
-    hipLaunchKernelGGL(resize_kernel<LoaderWords>, dim3(rblocks, (unsigned)nb), dim3(kThreads), 0, s, ra, D, H, W, wsc,
+    hipLaunchKernelGGL(resize_kernel<LoaderWords>, dim3(resize_blocks(V), (unsigned)nb), dim3(kThreads), 0, s, ra, D, H, W, wsc,
                        static_cast<__half*>(image) + (size_t)b0 * 2 * V, label_map ? label_map + (size_t)b0 * V : nullptr);
-  }
-  hipLaunchKernelGGL(loader_crop_kernel, dim3((unsigned)((B * 3 + 63) / 64)), dim3(64), 0, s, ws, B, D, H, W, crop_indexes);
+  });
+  launch_crop(s, ws + 4, kWsWords, B, D, H, W, crop_indexes);
   MICF_RETURN_LAUNCH();
 }

@@ -1,7 +1,9 @@
-// volume_loader_common.h -- what volume_loader.hip (min-max only) and volume_normalise.hip (min-max / z-score / percentile clip per
-// channel) share: the descriptors that travel as kernel arguments, the order-preserving keys, the min / max pass over a raw
-// volume, the resize + label + crop-extent pass templated on the per-channel normaliser, the crop finish and the host-side
-// argument checks.  Everything lives in an unnamed namespace, so each of the two files gets its own copy; nothing uses scratch.
+// volume_loader_common.h -- what volume_loader.hip (min-max only), volume_normalise.hip (min-max / z-score / percentile clip per
+// channel) and volume_affine.hip (an affine map in the resample) share: the descriptors that travel as kernel arguments, the
+// order-preserving keys, the min / max pass over a raw volume, the resize + label + crop-extent pass templated on the per-channel
+// normaliser and the pieces volume_affine.hip's resample reuses (crop extents, label lookup), the zero and crop kernels, and the host
+// side: argument checks and the iterator over chunks of samples.  Everything lives in an unnamed namespace, so each including file
+// gets its own copy; nothing uses scratch.
 #pragma once
 #include <hip/hip_fp16.h>
 
@@ -64,21 +66,23 @@ __device__ __forceinline__ VecSpan vec_span(const void* p, int64_t n, int es) {
   return s;
 }
 
+// The 16-byte vectors of a volume that fall to this thread, four loads in flight.
+template <class F>
+__device__ __forceinline__ void for_each_vec(const VecSpan& sp, int64_t g0, int64_t gs, F&& f) {
+  int64_t i = g0;
+  for (; i + 3 * gs < sp.nvec; i += 4 * gs) {
+    const uint4 q0 = sp.vec[i], q1 = sp.vec[i + gs], q2 = sp.vec[i + 2 * gs], q3 = sp.vec[i + 3 * gs];
+    f(q0); f(q1); f(q2); f(q3);
+  }
+  for (; i < sp.nvec; i += gs) f(sp.vec[i]);
+}
+
 // ---- min / max of one raw image volume: two integer atomicMax per block on keys[0] (max of key) and keys[1] (max of ~key) -------
 __device__ __forceinline__ void minmax_body(const RawVol& vol, uint32_t* keys, uint32_t* s_red /* [2 * kWaves] */) {
   const int tid = threadIdx.x;
-  const int64_t n = vol.n;
   const bool f32 = vol.dtype == MICF_LOADER_F32;
-  const int es = f32 ? 4 : 2, per = 16 / es;
-  const char* base = static_cast<const char*>(vol.p);
-  // [0, head) scalar, then nvec aligned 16-byte vectors, then the scalar tail
-  int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(base) & 15)) & 15) / es;
-  if (head > n) head = n;
-  const int64_t nvec = (n - head) / per;
-  const int64_t tail0 = head + nvec * per;
-  const uint4* vec = reinterpret_cast<const uint4*>(base + head * es);
+  const VecSpan sp = vec_span(vol.p, vol.n, f32 ? 4 : 2);
   const int64_t g0 = (int64_t)blockIdx.x * kThreads + tid, gs = (int64_t)gridDim.x * kThreads;
-  const int nscalar = (int)(head + (n - tail0));                 // < 16
   uint32_t kmax, kmin_inv;
   if (f32) {
     const float* src = static_cast<const float*>(vol.p);
@@ -89,14 +93,9 @@ __device__ __forceinline__ void minmax_body(const RawVol& vol, uint32_t* keys, u
 #pragma unroll
       for (int j = 0; j < 4; ++j) { lo[j] = fminf(lo[j], f[j]); hi[j] = fmaxf(hi[j], f[j]); }
     };
-    int64_t i = g0;
-    for (; i + 3 * gs < nvec; i += 4 * gs) {
-      const uint4 q0 = vec[i], q1 = vec[i + gs], q2 = vec[i + 2 * gs], q3 = vec[i + 3 * gs];
-      take(q0); take(q1); take(q2); take(q3);
-    }
-    for (; i < nvec; i += gs) take(vec[i]);
-    if (blockIdx.x == 0 && tid < nscalar) {
-      const float x = src[tid < head ? tid : tail0 + (tid - head)];
+    for_each_vec(sp, g0, gs, take);
+    if (blockIdx.x == 0 && tid < sp.nscalar) {
+      const float x = src[tid < sp.head ? tid : sp.tail0 + (tid - sp.head)];
       lo[0] = fminf(lo[0], x); hi[0] = fmaxf(hi[0], x);
     }
     kmax = key_f32(fmaxf(fmaxf(hi[0], hi[1]), fmaxf(hi[2], hi[3])));
@@ -111,17 +110,12 @@ __device__ __forceinline__ void minmax_body(const RawVol& vol, uint32_t* keys, u
       lo = __builtin_elementwise_min(lo, h);
       hi = __builtin_elementwise_max(hi, h);
     };
-    int64_t i = g0;
-    for (; i + 3 * gs < nvec; i += 4 * gs) {
-      const uint4 q0 = vec[i], q1 = vec[i + gs], q2 = vec[i + 2 * gs], q3 = vec[i + 3 * gs];
-      take(q0); take(q1); take(q2); take(q3);
-    }
-    for (; i < nvec; i += gs) take(vec[i]);
+    for_each_vec(sp, g0, gs, take);
     int mn = lo[0], mx = hi[0];
 #pragma unroll
     for (int j = 1; j < 8; ++j) { mn = lo[j] < mn ? lo[j] : mn; mx = hi[j] > mx ? hi[j] : mx; }
-    if (blockIdx.x == 0 && tid < nscalar) {
-      const int x = src[tid < head ? tid : tail0 + (tid - head)];
+    if (blockIdx.x == 0 && tid < sp.nscalar) {
+      const int x = src[tid < sp.head ? tid : sp.tail0 + (tid - sp.head)];
       mn = x < mn ? x : mn; mx = x > mx ? x : mx;
     }
     kmax = key_i16(mx);
@@ -207,6 +201,42 @@ __device__ __forceinline__ float trilinear(const Vol3& v, const N& nm, int z, in
   return u0 * lz0 + u1 * lz1;
 }
 
+// The crop extents of the non-zero voxels one thread has seen: running maxima of (index + 1) and of (extent - index) on z y x,
+// 0 = no non-zero voxel seen.
+struct Extents {
+  uint32_t ez = 0, ey = 0, ex = 0, fz = 0, fy = 0, fx = 0;
+  __device__ __forceinline__ void see(int z, int y, int x, int D, int H, int W) {
+    ez = max(ez, (uint32_t)(z + 1)); fz = max(fz, (uint32_t)(D - z));
+    ey = max(ey, (uint32_t)(y + 1)); fy = max(fy, (uint32_t)(H - y));
+    ex = max(ex, (uint32_t)(x + 1)); fx = max(fx, (uint32_t)(W - x));
+  }
+  // Every thread of the block calls it: wave shuffles, one LDS atomicMax per wave and word on s_ext (six words, zeroed before a
+  // barrier), then the block's six global atomicMax on the sample's crop words dst.
+  __device__ __forceinline__ void flush(uint32_t* s_ext, uint32_t* dst) {
+    const int tid = threadIdx.x;
+    ez = wave_umax(ez); ey = wave_umax(ey); ex = wave_umax(ex);
+    fz = wave_umax(fz); fy = wave_umax(fy); fx = wave_umax(fx);
+    if ((tid & 63) == 0) {
+      atomicMax(&s_ext[0], ez); atomicMax(&s_ext[1], ey); atomicMax(&s_ext[2], ex);
+      atomicMax(&s_ext[3], fz); atomicMax(&s_ext[4], fy); atomicMax(&s_ext[5], fx);
+    }
+    __syncthreads();
+    if (tid < 6 && s_ext[tid] != 0) atomicMax(dst + tid, s_ext[tid]);
+  }
+};
+
+// element `off` of a raw label volume
+__device__ __forceinline__ int raw_label(const Vol3& lv, int64_t off) {
+  return lv.dtype == MICF_LOADER_I32 ? static_cast<const int32_t*>(lv.p)[off] : (int)static_cast<const int16_t*>(lv.p)[off];
+}
+
+// raw label value -> class: 0 for 0, k for a.vals[k - 1], 255 elsewhere
+__device__ __forceinline__ int label_class(const ResizeArgs& a, int val) {
+  int cls = val == 0 ? 0 : 255;
+  for (int k = 0; k < a.nvals; ++k) cls = val == a.vals[k] ? k + 1 : cls;
+  return cls;
+}
+
 // micf_volume_loader's workspace: per sample ct {max key, max ~key}, mr {..}, crop {max+1 z y x, extent-min z y x}
 constexpr int kWsWords = 10;
 struct LoaderWords {
@@ -236,52 +266,47 @@ __global__ __launch_bounds__(kThreads) void resize_kernel(ResizeArgs a, int D, i
   __half* img = image + (size_t)blockIdx.y * 2 * V;
   if (tid < 6) s_ext[tid] = 0;
   __syncthreads();
-  // running maxima of (index + 1) and of (extent - index): 0 = no non-zero voxel seen
-  uint32_t ez = 0, ey = 0, ex = 0, fz = 0, fy = 0, fx = 0;
+  Extents ext;
   for (int v = blockIdx.x * kThreads + tid; v < V; v += gridDim.x * kThreads) {
     const int x = v % W, t = v / W, y = t % H, z = t / H;
     const float c0 = ct32 ? trilinear<true>(sd.ct, nct, z, y, x, D, H, W) : trilinear<false>(sd.ct, nct, z, y, x, D, H, W);
     const float c1 = mr32 ? trilinear<true>(sd.mr, nmr, z, y, x, D, H, W) : trilinear<false>(sd.mr, nmr, z, y, x, D, H, W);
     if (P::stores(wsb, 0)) img[v] = __float2half_rn(c0);
     if (P::stores(wsb, 1)) img[(size_t)V + v] = __float2half_rn(c1);
-    if (c0 != 0.0f || c1 != 0.0f) {                              // (true for NaN, as numpy's `!= 0`)
-      ez = max(ez, (uint32_t)(z + 1)); fz = max(fz, (uint32_t)(D - z));
-      ey = max(ey, (uint32_t)(y + 1)); fy = max(fy, (uint32_t)(H - y));
-      ex = max(ex, (uint32_t)(x + 1)); fx = max(fx, (uint32_t)(W - x));
-    }
+    if (c0 != 0.0f || c1 != 0.0f) ext.see(z, y, x, D, H, W);       // (true for NaN, as numpy's `!= 0`)
     if (label_map) {
       const Vol3& lv = sd.lab;
       const int sz = nearest_axis(z, lv.d, D), sy = nearest_axis(y, lv.h, H), sx = nearest_axis(x, lv.w, W);
-      const int64_t off = ((int64_t)sz * lv.h + sy) * lv.w + sx;
-      const int val = lv.dtype == MICF_LOADER_I32 ? static_cast<const int32_t*>(lv.p)[off]
-                                                  : (int)static_cast<const int16_t*>(lv.p)[off];
-      int cls = val == 0 ? 0 : 255;
-      for (int k = 0; k < a.nvals; ++k) cls = val == a.vals[k] ? k + 1 : cls;
-      label_map[(size_t)blockIdx.y * V + v] = (uint8_t)cls;
+      const int val = raw_label(lv, ((int64_t)sz * lv.h + sy) * lv.w + sx);
+      label_map[(size_t)blockIdx.y * V + v] = (uint8_t)label_class(a, val);
     }
   }
-  ez = wave_umax(ez); ey = wave_umax(ey); ex = wave_umax(ex);
-  fz = wave_umax(fz); fy = wave_umax(fy); fx = wave_umax(fx);
-  if ((tid & 63) == 0) {
-    atomicMax(&s_ext[0], ez); atomicMax(&s_ext[1], ey); atomicMax(&s_ext[2], ex);
-    atomicMax(&s_ext[3], fz); atomicMax(&s_ext[4], fy); atomicMax(&s_ext[5], fx);
-  }
-  __syncthreads();
-  if (tid < 6 && s_ext[tid] != 0) atomicMax(P::ext(wsb) + tid, s_ext[tid]);
+  ext.flush(s_ext, P::ext(wsb));
 }
 
-// ---- crop_indexes of one (sample, axis) from the sample's six crop words ---------------------------------------------------------
-__device__ __forceinline__ void crop_body(const uint32_t* ext, int ax, int D, int H, int W, int32_t* crop2) {
-  const int extent = ax == 0 ? D : (ax == 1 ? H : W);
-  const uint32_t e = ext[ax], f = ext[3 + ax];
+// ---- the running maxima, counts and sums of a workspace start at 0.  A kernel, not hipMemsetAsync: captured into a graph, the memset
+// node of the plain loader's few words left stale words behind at the second replay on ROCm 7.2
+// (tests/test_gpu_loader.py::test_capture_and_replay_under_a_graph caught it).
+__global__ void loader_zero_kernel(uint32_t* ws, int64_t words) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) ws[i] = 0;
+}
+
+// ---- crop_indexes (max(0, min - 1), max + 1) of every (sample, axis), (0, 0) where the image is all zero.  Sample b's six crop
+// words lie at ext + b * stride: the loader format's at ws + 4, stride kWsWords; a record's at recs->ext, stride sizeof(SampleRec) / 4.
+__global__ void loader_crop_kernel(const uint32_t* ext, int stride, int B, int D, int H, int W, int32_t* crop) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * 3) return;
+  const int ax = i % 3, extent = ax == 0 ? D : (ax == 1 ? H : W);
+  const uint32_t* w = ext + (size_t)(i / 3) * stride;
+  const uint32_t e = w[ax], f = w[3 + ax];
   int lo = 0, hi = 0;
   if (e != 0) {
     const int mn = extent - (int)f;
     lo = mn - 1 > 0 ? mn - 1 : 0;
     hi = (int)e;
   }
-  crop2[0] = lo;
-  crop2[1] = hi;
+  crop[i * 2] = lo;
+  crop[i * 2 + 1] = hi;
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
@@ -330,23 +355,6 @@ inline int check_call(const micf_loader_sample* samples, int B, int D, int H, in
 
 inline Vol3 vol3(const void* p, const int32_t* shape, int dtype) { return Vol3{p, shape[0], shape[1], shape[2], dtype}; }
 
-// The chunk's descriptors; unused slots repeat the chunk's first sample (never launched).  -> the most bytes of one image volume.
-inline int64_t fill_chunk(const micf_loader_sample* samples, int b0, int nb, MinMaxArgs& ma, ResizeArgs& ra) {
-  int64_t most = 0;
-  for (int i = 0; i < kChunk; ++i) {
-    const micf_loader_sample& sm = samples[b0 + (i < nb ? i : 0)];
-    ma.v[2 * i] = RawVol{sm.ct, (int64_t)sm.ct_shape[0] * sm.ct_shape[1] * sm.ct_shape[2], sm.ct_dtype, 0};
-    ma.v[2 * i + 1] = RawVol{sm.mr, (int64_t)sm.mr_shape[0] * sm.mr_shape[1] * sm.mr_shape[2], sm.mr_dtype, 0};
-    ra.s[i] = SampleDesc{vol3(sm.ct, sm.ct_shape, sm.ct_dtype), vol3(sm.mr, sm.mr_shape, sm.mr_dtype),
-                         vol3(sm.label, sm.label_shape, sm.label_dtype)};
-    for (int c = 0; c < 2; ++c) {
-      const int64_t bytes = ma.v[2 * i + c].n * elem_size(ma.v[2 * i + c].dtype);
-      most = bytes > most ? bytes : most;
-    }
-  }
-  return most;
-}
-
 // blocks of a pass over `bytes` of raw volume: four 16-byte loads per thread and trip, at most 1024
 __host__ __device__ inline unsigned pass_blocks(int64_t bytes) {
   const int64_t mb = (bytes / 16 + 4 * kThreads - 1) / (4 * kThreads);
@@ -361,6 +369,38 @@ inline unsigned resize_blocks(int64_t V) {
 inline void fill_label_values(ResizeArgs& ra, const int32_t* label_values, int num_label_values) {
   ra.nvals = num_label_values;
   for (int i = 0; i < MICF_LOADER_MAX_LABEL_VALUES; ++i) ra.vals[i] = i < num_label_values ? label_values[i] : 0;
+}
+
+// The batch in chunks of at most kChunk samples: f(b0, nb, blocks) with ma / ra holding the descriptors of samples [b0, b0 + nb)
+// (unused slots repeat the chunk's first sample and are never launched) and blocks = pass_blocks of the chunk's largest image volume.
+template <class F>
+inline void for_each_chunk(const micf_loader_sample* samples, int B, MinMaxArgs& ma, ResizeArgs& ra, F&& f) {
+  for (int b0 = 0; b0 < B; b0 += kChunk) {
+    const int nb = B - b0 < kChunk ? B - b0 : kChunk;
+    int64_t most = 0;
+    for (int i = 0; i < kChunk; ++i) {
+      const micf_loader_sample& sm = samples[b0 + (i < nb ? i : 0)];
+      ma.v[2 * i] = RawVol{sm.ct, (int64_t)sm.ct_shape[0] * sm.ct_shape[1] * sm.ct_shape[2], sm.ct_dtype, 0};
+      ma.v[2 * i + 1] = RawVol{sm.mr, (int64_t)sm.mr_shape[0] * sm.mr_shape[1] * sm.mr_shape[2], sm.mr_dtype, 0};
+      ra.s[i] = SampleDesc{vol3(sm.ct, sm.ct_shape, sm.ct_dtype), vol3(sm.mr, sm.mr_shape, sm.mr_dtype),
+                           vol3(sm.label, sm.label_shape, sm.label_dtype)};
+      for (int c = 0; c < 2; ++c) {
+        const int64_t bytes = ma.v[2 * i + c].n * elem_size(ma.v[2 * i + c].dtype);
+        most = bytes > most ? bytes : most;
+      }
+    }
+    f(b0, nb, pass_blocks(most));
+  }
+}
+
+inline void launch_zero(hipStream_t s, void* ws, int64_t words) {
+  const int64_t zb = (words + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(loader_zero_kernel, dim3((unsigned)(zb < 1024 ? zb : 1024)), dim3(kThreads), 0, s, static_cast<uint32_t*>(ws),
+                     words);
+}
+
+inline void launch_crop(hipStream_t s, const uint32_t* ext, int stride, int B, int D, int H, int W, int32_t* crop_indexes) {
+  hipLaunchKernelGGL(loader_crop_kernel, dim3((unsigned)((B * 3 + 63) / 64)), dim3(64), 0, s, ext, stride, B, D, H, W, crop_indexes);
 }
 
 }  // namespace

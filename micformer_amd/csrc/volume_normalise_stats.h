@@ -1,6 +1,7 @@
 // volume_normalise_stats.h -- the statistics passes of the loader's normalisations (min / max, moments, radix select, finish) and the
-// per-channel normaliser of the resize, moved here verbatim from volume_normalise.hip so that volume_affine.hip runs the very same
-// passes; volume_normalise.hip has the launch plan and the rules.  Unnamed namespace: each including file gets its own copy.
+// per-channel normaliser of the resize, and the host side that volume_normalise.hip and volume_affine.hip share: their common
+// argument checks, the view of the workspace and the driver of a call (run_stats_loader), which each of the two hands its own
+// resample step.  volume_normalise.hip has the launch plan and the rules.  Unnamed namespace: each including file gets its own copy.
 #pragma once
 #include "volume_loader_common.h"
 #include "../../include/micformer_normalise.h"
@@ -42,11 +43,7 @@ Layout layout(int B) {
 
 struct Modes { int m[2]; };
 
-// ---- 0. zero ------------------------------------------------------------------------------------------------------------------
-// (a kernel, not hipMemsetAsync: see volume_loader.hip)
-__global__ void norm_zero_kernel(uint32_t* ws, int64_t words) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (int64_t)gridDim.x * blockDim.x) ws[i] = 0;
-}
+// ---- 0. zero: loader_zero_kernel (volume_loader_common.h) over L.zero_words ------------------------------------------------------
 
 // ---- 1. min / max ---------------------------------------------------------------------------------------------------------------
 // grid (blocks, volumes of the chunk) for every statistics kernel; volume y is channel y & 1 of sample y >> 1.
@@ -54,17 +51,6 @@ __global__ __launch_bounds__(kThreads) void norm_minmax_kernel(MinMaxArgs a, Mod
   __shared__ uint32_t s_red[2 * kWaves];
   if (md.m[blockIdx.y & 1] != MICF_NORM_MINMAX) return;
   minmax_body(a.v[blockIdx.y], words + (size_t)(blockIdx.y >> 1) * kWsWords + 2 * (blockIdx.y & 1), s_red);
-}
-
-// The 16-byte vectors of a volume that fall to this thread, four loads in flight.
-template <class F>
-__device__ __forceinline__ void for_each_vec(const VecSpan& sp, int64_t g0, int64_t gs, F&& f) {
-  int64_t i = g0;
-  for (; i + 3 * gs < sp.nvec; i += 4 * gs) {
-    const uint4 q0 = sp.vec[i], q1 = sp.vec[i + gs], q2 = sp.vec[i + 2 * gs], q3 = sp.vec[i + 3 * gs];
-    f(q0); f(q1); f(q2); f(q3);
-  }
-  for (; i < sp.nvec; i += gs) f(sp.vec[i]);
 }
 
 // ---- 2. moments -----------------------------------------------------------------------------------------------------------------
@@ -437,24 +423,75 @@ struct NormWords {
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 inline bool valid_mode(int m) { return m == MICF_NORM_MINMAX || m == MICF_NORM_ZSCORE || m == MICF_NORM_PERCENTILE; }
 
-// The statistics launches of one chunk of `nb` samples (steps 1-4 of the launch plan); every pointer is the chunk's own.
+// What micf_volume_loader_norm and micf_volume_loader_affine check in front of check_call.
+inline int check_norm_args(int ct_mode, int mr_mode, double p_low, double p_high, const double* stats) {
+  if (!valid_mode(ct_mode) || !valid_mode(mr_mode)) return MICF_EINVAL;
+  if (!(0.0 <= p_low && p_low < p_high && p_high <= 100.0)) return MICF_EINVAL;      // (false for NaN)
+  if (reinterpret_cast<uintptr_t>(stats) & 7) return MICF_EINVAL;
+  return MICF_OK;
+}
+
+// The workspace as layout(B) carves it, and the call's optional `stats`; chunk(b0): the same from sample b0 on.
+struct WsView {
+  uint32_t* words;
+  SampleRec* recs;
+  uint32_t* hist;
+  Mom* partials;
+  double* stats;
+  WsView chunk(int b0) const {
+    return WsView{words + (size_t)b0 * kWsWords, recs + b0, hist + (size_t)b0 * 2 * kRanks * kBins,
+                  partials + (size_t)b0 * 2 * kMaxPartials, stats ? stats + (size_t)b0 * 4 : nullptr};
+  }
+};
+inline WsView ws_view(void* workspace, const Layout& L, double* stats) {
+  char* ws = static_cast<char*>(workspace);
+  return WsView{reinterpret_cast<uint32_t*>(ws), reinterpret_cast<SampleRec*>(ws + L.recs), reinterpret_cast<uint32_t*>(ws + L.hist),
+                reinterpret_cast<Mom*>(ws + L.partials), stats};
+}
+
+// The statistics launches of one chunk of `nb` samples (steps 1-4 of the launch plan) on the chunk's view of the workspace.
 inline void launch_statistics(hipStream_t s, const MinMaxArgs& ma, const Modes& md, int nb, unsigned blocks, double p_low,
-                              double p_high, uint32_t* w0, SampleRec* rc0, uint32_t* h0, Mom* p0, double* stats0) {
+                              double p_high, const WsView& c) {
   const dim3 grid(blocks, (unsigned)(2 * nb)), vols((unsigned)(2 * nb));
   const bool any_minmax = md.m[0] == MICF_NORM_MINMAX || md.m[1] == MICF_NORM_MINMAX;
   const bool any_zscore = md.m[0] == MICF_NORM_ZSCORE || md.m[1] == MICF_NORM_ZSCORE;
   const bool any_pct = md.m[0] == MICF_NORM_PERCENTILE || md.m[1] == MICF_NORM_PERCENTILE;
-  if (any_minmax) hipLaunchKernelGGL(norm_minmax_kernel, grid, dim3(kThreads), 0, s, ma, md, w0);
-  if (any_zscore) hipLaunchKernelGGL(norm_moments_kernel, grid, dim3(kThreads), 0, s, ma, md, rc0, p0);
+  if (any_minmax) hipLaunchKernelGGL(norm_minmax_kernel, grid, dim3(kThreads), 0, s, ma, md, c.words);
+  if (any_zscore) hipLaunchKernelGGL(norm_moments_kernel, grid, dim3(kThreads), 0, s, ma, md, c.recs, c.partials);
   if (any_pct) {
     bool third = false;                                        // a float32 volume among the chunk's percentile channels?
     for (int v = 0; v < 2 * nb; ++v) third |= md.m[v & 1] == MICF_NORM_PERCENTILE && ma.v[v].dtype == MICF_LOADER_F32;
     for (int pass = 0; pass < (third ? 3 : 2); ++pass) {
-      hipLaunchKernelGGL(norm_hist_kernel, grid, dim3(kThreads), 0, s, ma, md, pass, rc0, h0);
-      hipLaunchKernelGGL(norm_scan_kernel, vols, dim3(kThreads), 0, s, ma, md, pass, p_low, p_high, rc0, h0);
+      hipLaunchKernelGGL(norm_hist_kernel, grid, dim3(kThreads), 0, s, ma, md, pass, c.recs, c.hist);
+      hipLaunchKernelGGL(norm_scan_kernel, vols, dim3(kThreads), 0, s, ma, md, pass, p_low, p_high, c.recs, c.hist);
     }
   }
-  hipLaunchKernelGGL(norm_finish_kernel, vols, dim3(64), 0, s, ma, md, p_low, p_high, w0, rc0, p0, stats0);
+  hipLaunchKernelGGL(norm_finish_kernel, vols, dim3(64), 0, s, ma, md, p_low, p_high, c.words, c.recs, c.partials, c.stats);
+}
+
+// micf_volume_loader_norm and micf_volume_loader_affine after their checks: zero, then per chunk the statistics passes and the
+// entry's own resample(ra, c, b0, grid, image0, label0) -- c, image0 and label0 the chunk's, grid (blocks, samples of the chunk) --
+// then the crop finish on the loader-format words (words_ext) or on the records.
+template <class R>
+inline int run_stats_loader(const micf_loader_sample* samples, int B, int D, int H, int W, const int32_t* label_values,
+                            int num_label_values, const Modes& md, double p_low, double p_high, void* workspace, void* image,
+                            uint8_t* label_map, int32_t* crop_indexes, double* stats, hipStream_t s, bool words_ext, R&& resample) {
+  const Layout L = layout(B);
+  const WsView ws = ws_view(workspace, L, stats);
+  const int64_t V = (int64_t)D * H * W;
+  launch_zero(s, workspace, L.zero_words);
+  MinMaxArgs ma;
+  ResizeArgs ra;
+  fill_label_values(ra, label_values, num_label_values);
+  for_each_chunk(samples, B, ma, ra, [&](int b0, int nb, unsigned blocks) {
+    const WsView c = ws.chunk(b0);
+    launch_statistics(s, ma, md, nb, blocks, p_low, p_high, c);
+    resample(ra, c, b0, dim3(resize_blocks(V), (unsigned)nb), static_cast<__half*>(image) + (size_t)b0 * 2 * V,
+             label_map ? label_map + (size_t)b0 * V : nullptr);
+  });
+  if (words_ext) launch_crop(s, ws.words + 4, kWsWords, B, D, H, W, crop_indexes);
+  else launch_crop(s, ws.recs->ext, (int)(sizeof(SampleRec) / 4), B, D, H, W, crop_indexes);
+  MICF_RETURN_LAUNCH();
 }
 
 }  // namespace

@@ -145,29 +145,22 @@ def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, o
             raise ValueError("out label_map must be given exactly when the samples have labels")
         label_map = _args.out_tensor(out[1], "out label_map", (B, D, H, W), torch.uint8, device) if has_label else None
         crop = _args.out_tensor(out[2], "out crop_indexes", (B, 3, 2), torch.int32, device)
-    if affine is not None:
-        if affine.device != device:
-            raise ValueError(f"affine is on {affine.device}, the batch on {device}")
-        stats = torch.empty((B, 2, 2), dtype=torch.float64, device=device) if return_stats else None
-        nbytes = _lib.query_bytes("micf_volume_loader_affine_workspace", B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _lib.call_on(device, "micf_volume_loader_affine", ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals,
-                     ct_mode, mr_mode, p_low, p_high, ws.data_ptr(), nbytes, image.data_ptr(),
-                     None if label_map is None else label_map.data_ptr(), crop.data_ptr(),
-                     None if stats is None else stats.data_ptr(), affine.data_ptr(), per_modality, pad)
-        return (image, label_map, crop, stats) if return_stats else (image, label_map, crop)
-    if (ct_mode, mr_mode) == (normalise.MINMAX, normalise.MINMAX) and not return_stats:
-        nbytes = _lib.query_bytes("micf_volume_loader_workspace", B)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _lib.call_on(device, "micf_volume_loader", ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals,
-                     ws.data_ptr(), nbytes, image.data_ptr(), None if label_map is None else label_map.data_ptr(), crop.data_ptr())
-        return image, label_map, crop
+    if affine is not None and affine.device != device:
+        raise ValueError(f"affine is on {affine.device}, the batch on {device}")
+    plain = affine is None and (ct_mode, mr_mode) == (normalise.MINMAX, normalise.MINMAX) and not return_stats
+    entry = "micf_volume_loader" + ("" if plain else "_norm" if affine is None else "_affine")
     stats = torch.empty((B, 2, 2), dtype=torch.float64, device=device) if return_stats else None
-    nbytes = _lib.query_bytes("micf_volume_loader_norm_workspace", B)
+    nbytes = _lib.query_bytes(entry + "_workspace", B)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    _lib.call_on(device, "micf_volume_loader_norm", ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals, ct_mode,
-                 mr_mode, p_low, p_high, ws.data_ptr(), nbytes, image.data_ptr(),
-                 None if label_map is None else label_map.data_ptr(), crop.data_ptr(), None if stats is None else stats.data_ptr())
+    args = [ctypes.addressof(items), B, D, H, W, ctypes.addressof(vals), nvals]
+    if not plain:
+        args += [ct_mode, mr_mode, p_low, p_high]
+    args += [ws.data_ptr(), nbytes, image.data_ptr(), None if label_map is None else label_map.data_ptr(), crop.data_ptr()]
+    if not plain:
+        args.append(None if stats is None else stats.data_ptr())
+    if affine is not None:
+        args += [affine.data_ptr(), per_modality, pad]
+    _lib.call_on(device, entry, *args)
     return (image, label_map, crop, stats) if return_stats else (image, label_map, crop)
 
 

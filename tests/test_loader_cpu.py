@@ -111,19 +111,28 @@ def test_workspace_query_is_pure_and_validates():
 
 
 def test_bad_arguments_return_codes_before_any_launch():
-    from micformer_amd import loader
-    lib = loader.lib
+    """The calls micf_volume_loader rejects and the code each returns; micf_volume_loader_norm and micf_volume_loader_affine, given
+    valid normaliser / `stats` / affine arguments next to them and their own workspace size, return the same codes."""
+    from micformer_amd import affine, loader, normalise
+    fake = 1 << 20
+    _rejected_calls(loader, loader.lib.micf_volume_loader, loader.lib.micf_volume_loader_workspace(1), (), ())
+    norm = (normalise.ZSCORE, normalise.PERCENTILE, 1.0, 99.0)
+    _rejected_calls(loader, normalise.lib.micf_volume_loader_norm, normalise.lib.micf_volume_loader_norm_workspace(1), norm, (None,))
+    _rejected_calls(loader, affine.lib.micf_volume_loader_affine, affine.lib.micf_volume_loader_affine_workspace(1), norm,
+                    (None, fake, 0, affine.padding("zeros")))
+
+
+def _rejected_calls(loader, fn, ws, norm, tail):
+    """fn(<the common head>, *norm, <workspace and outputs>, *tail, stream) for every rejected call of the table."""
     EINVAL, EUNSUP = -1, -2
     fake = 1 << 20
     vals = (ctypes.c_int32 * 7)(*loader.MMWHS_LABEL_VALUES)
-    ws = lib.micf_volume_loader_workspace(1)
 
     def call(sample=None, B=1, size=(16, 16, 16), values=vals, nvals=7, workspace=fake, ws_bytes=ws, image=fake, label_map=fake,
              crop=fake, samples_ptr=True):
         s = sample if sample is not None else _sample(loader)
-        return lib.micf_volume_loader(ctypes.addressof(s) if samples_ptr else None, B, *size,
-                                      None if values is None else ctypes.addressof(values), nvals, workspace, ws_bytes, image,
-                                      label_map, crop, None)
+        return fn(ctypes.addressof(s) if samples_ptr else None, B, *size, None if values is None else ctypes.addressof(values),
+                  nvals, *norm, workspace, ws_bytes, image, label_map, crop, *tail, None)
 
     assert call(samples_ptr=False) == EINVAL
     assert call(B=0) == EINVAL

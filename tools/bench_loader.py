@@ -7,7 +7,9 @@ one JSON line per batch size.
 ms_per_call: device events around >= min-seconds of calls after warm-up (the whole call: workspace zeroing, min/max, resize + label + crop,
 crop finish).  minmax_ms: the same call with a 1x1x1 target, i.e. the full read of the raw image volumes plus launch overheads;
 minmax_GBps: the raw image bytes of the batch (the bytes that pass must read) over that time.  resize_ms: the difference of the two.
-Per-kernel times proper come from a kernel trace of this script (loader_minmax_kernel / loader_resize_kernel / loader_crop_kernel).
+Per-kernel times proper come from a kernel trace of this script (loader_zero_kernel / loader_minmax_kernel /
+resize_kernel<LoaderWords> / loader_crop_kernel; with --normalisation norm_minmax_kernel, norm_moments_kernel, norm_hist_kernel,
+norm_scan_kernel, norm_finish_kernel and resize_kernel<NormWords>; with --affine affine_resample_kernel).
 cpu_s: the CPU referee (tests/loader_ref.py: numpy + F.interpolate, the reference's own operators) for ONE sample on this host.
 --normalisation other than the default "minmax" times the same call through micf_volume_loader_norm (csrc/volume_normalise.hip):
 the 1x1x1-target call is then the statistics passes of that mode (moments; histogram + scan per digit), reported as stats_ms /
