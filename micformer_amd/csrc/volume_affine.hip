@@ -1,9 +1,9 @@
 // volume_affine.hip -- the volume loader with an affine map in its resample pass (include/micformer_affine.h): every output voxel
 // reads the raw CT / MR / label arrays at theta . (its normalised coordinate), F.affine_grid + F.grid_sample(align_corners=False),
 // with the normalisation of volume_normalise.hip applied to each tap.  The coordinate, clamp and index arithmetic is
-// affine_coords.h's (host-callable); everything else but the resample kernel -- the statistics passes, the per-channel normaliser,
-// the crop extents and label lookup, the host sequence (run_stats_loader) -- is volume_normalise_stats.h's and
-// volume_loader_common.h's.
+// affine_coords.h's (host-callable); what happens to a source coordinate (taps, label, stores, extents) is affine_taps.h's, shared
+// with volume_elastic.hip; everything else but the resample kernel -- the statistics passes, the per-channel normaliser, the host
+// sequence (run_stats_loader) -- is volume_normalise_stats.h's and volume_loader_common.h's.
 //
 // Launch plan of micf_volume_loader_affine (batched over the samples, 8 per launch, no host round trip):
 //   0 zero, 1-4 the statistics passes the two modes need and their finish: volume_normalise.hip's plan, unchanged (the statistics
@@ -15,39 +15,10 @@
 //                resize_kernel's Extents
 //   6 crop       loader_crop_kernel on the records: extents -> crop_indexes
 // Everything that crosses threads is an integer count, sum or maximum, or is merged in a fixed order: bit-identical from run to run.
-#include "volume_normalise_stats.h"
-#include "affine_coords.h"
+#include "affine_taps.h"
 #include "../../include/micformer_affine.h"
 
 namespace {
-
-using micf_affine::LinearTaps;
-
-struct AxisIndex { float z, y, x; };
-
-// index of the normalised source coordinate (sx, sy, sz) in an array of shape (d, h, w)
-__device__ __forceinline__ AxisIndex source_indices(const Vol3& v, float sx, float sy, float sz) {
-  return AxisIndex{micf_affine::source_index(sz, v.d), micf_affine::source_index(sy, v.h), micf_affine::source_index(sx, v.w)};
-}
-
-// separable trilinear sum over the 8 taps, w fastest (trilinear()'s order); a tap outside the array counts 0
-template <bool F32>
-__device__ __forceinline__ float affine_trilinear(const Vol3& v, const NormAny& nm, const AxisIndex& i, bool border) {
-  const LinearTaps tz = micf_affine::linear_taps(i.z, v.d, border);
-  const LinearTaps ty = micf_affine::linear_taps(i.y, v.h, border);
-  const LinearTaps tx = micf_affine::linear_taps(i.x, v.w, border);
-  const int64_t r00 = ((int64_t)tz.i0 * v.h + ty.i0) * v.w, r01 = ((int64_t)tz.i0 * v.h + ty.i1) * v.w;
-  const int64_t r10 = ((int64_t)tz.i1 * v.h + ty.i0) * v.w, r11 = ((int64_t)tz.i1 * v.h + ty.i1) * v.w;
-  const bool i00 = tz.in0 && ty.in0, i01 = tz.in0 && ty.in1, i10 = tz.in1 && ty.in0, i11 = tz.in1 && ty.in1;
-  const float a00 = i00 && tx.in0 ? tap<F32>(v.p, r00 + tx.i0, nm) : 0.0f, b00 = i00 && tx.in1 ? tap<F32>(v.p, r00 + tx.i1, nm) : 0.0f;
-  const float a01 = i01 && tx.in0 ? tap<F32>(v.p, r01 + tx.i0, nm) : 0.0f, b01 = i01 && tx.in1 ? tap<F32>(v.p, r01 + tx.i1, nm) : 0.0f;
-  const float a10 = i10 && tx.in0 ? tap<F32>(v.p, r10 + tx.i0, nm) : 0.0f, b10 = i10 && tx.in1 ? tap<F32>(v.p, r10 + tx.i1, nm) : 0.0f;
-  const float a11 = i11 && tx.in0 ? tap<F32>(v.p, r11 + tx.i0, nm) : 0.0f, b11 = i11 && tx.in1 ? tap<F32>(v.p, r11 + tx.i1, nm) : 0.0f;
-  const float t00 = a00 * tx.w0 + b00 * tx.w1, t01 = a01 * tx.w0 + b01 * tx.w1;
-  const float t10 = a10 * tx.w0 + b10 * tx.w1, t11 = a11 * tx.w0 + b11 * tx.w1;
-  const float u0 = t00 * ty.w0 + t01 * ty.w1, u1 = t10 * ty.w0 + t11 * ty.w1;
-  return u0 * tz.w0 + u1 * tz.w1;
-}
 
 // ---- 5. resample ------------------------------------------------------------------------------------------------------------------
 // grid (blocks, samples of the chunk); recs / theta / image / label_map point at the chunk's first sample.  theta: per sample
@@ -79,32 +50,7 @@ __global__ __launch_bounds__(kThreads) void affine_resample_kernel(ResizeArgs a,
                 cz = micf_affine::map_row(tc + 8, nx, ny, nz);
     const float mx = micf_affine::map_row(tm, nx, ny, nz), my = micf_affine::map_row(tm + 4, nx, ny, nz),
                 mz = micf_affine::map_row(tm + 8, nx, ny, nz);
-    const bool cok = micf_affine::finite(cx) && micf_affine::finite(cy) && micf_affine::finite(cz);
-    const bool mok = micf_affine::finite(mx) && micf_affine::finite(my) && micf_affine::finite(mz);
-    float c0 = 0.0f, c1 = 0.0f;
-    if (cok) {
-      const AxisIndex i = source_indices(sd.ct, cx, cy, cz);
-      c0 = ct32 ? affine_trilinear<true>(sd.ct, nct, i, bd) : affine_trilinear<false>(sd.ct, nct, i, bd);
-    }
-    if (mok) {
-      const AxisIndex i = source_indices(sd.mr, mx, my, mz);
-      c1 = mr32 ? affine_trilinear<true>(sd.mr, nmr, i, bd) : affine_trilinear<false>(sd.mr, nmr, i, bd);
-    }
-    img[v] = __float2half_rn(c0);
-    img[(size_t)V + v] = __float2half_rn(c1);
-    if (c0 != 0.0f || c1 != 0.0f) ext.see(z, y, x, D, H, W);       // (true for NaN, as numpy's `!= 0`)
-    if (label_map) {
-      const Vol3& lv = sd.lab;
-      int val = 0;                                               // outside the array, or a non-finite coordinate: raw label 0
-      if (cok) {
-        const AxisIndex i = source_indices(lv, cx, cy, cz);
-        bool inz, iny, inx;
-        const int sz = micf_affine::nearest_tap(i.z, lv.d, bd, inz), sy = micf_affine::nearest_tap(i.y, lv.h, bd, iny),
-                  sx = micf_affine::nearest_tap(i.x, lv.w, bd, inx);
-        if (inz && iny && inx) val = raw_label(lv, ((int64_t)sz * lv.h + sy) * lv.w + sx);
-      }
-      label_map[(size_t)blockIdx.y * V + v] = (uint8_t)label_class(a, val);
-    }
+    resample_voxel(a, sd, nct, nmr, ct32, mr32, bd, cx, cy, cz, mx, my, mz, v, z, y, x, D, H, W, V, ext, img, label_map);
   }
   ext.flush(s_ext, rec->ext);
 }

@@ -11,6 +11,9 @@ Geometric augmentation rides in the same pass (micformer_amd/affine.py has the r
     theta = affine.draw_affine(len(samples), generator=g, device="cuda")    # [B, 3, 4]: rotate / zoom / translate per sample
     image, label_map, crop = loader.load_batch(samples, affine=theta, padding_mode="border")
     theta.copy_(affine.draw_affine(len(samples), generator=g))              # a graph captured with out= reads the new draws
+... and so does a smooth non-rigid deformation, composed with the map (micformer_amd/elastic.py; csrc/volume_elastic.hip):
+    field = elastic.draw_elastic(len(samples), generator=g, device="cuda")  # [B, 3, 7, 7, 7]: a vector per control point
+    image, label_map, crop = loader.load_batch(samples, displacement=field, field_interpolation="cubic", affine=theta)
 
 What is computed, per sample (each array is resized independently from its own shape):
   * min-max normalisation of each image volume over the whole volume, (x - min) / (max - min), with one IEEE float32 divide per
@@ -34,7 +37,7 @@ import ctypes
 
 import torch
 
-from . import _args, _lib, affine as _affine, normalise
+from . import _args, _lib, affine as _affine, elastic as _elastic, normalise
 
 MMWHS_LABEL_VALUES = (205, 420, 500, 550, 600, 820, 850)          # MMWHS.py:289; class k = label_values[k - 1], class 0 = label 0
 MAX_LABEL_VALUES = 254
@@ -89,27 +92,39 @@ def _label_values(label_values):
 
 
 def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, out=None, normalisation="minmax",
-               percentiles=(1, 99), return_stats=False, affine=None, padding_mode="zeros"):
+               percentiles=(1, 99), return_stats=False, displacement=None, field_interpolation="linear", affine=None,
+               padding_mode="zeros"):
     """samples: sequence of (ct, mr, ct_label | None), every array an own-shaped (d, h, w) CUDA tensor (images int16 / float32,
     labels int16 / int32), labels present for all samples or for none.  out: optional preallocated (image, label_map,
     crop_indexes) to write into.  normalisation: "minmax" | "zscore" | "percentile", or a (ct, mr) pair of them; percentiles:
     (low, high) of the "percentile" mode.  return_stats=True appends the float64 [B, 2, 2] statistics of the normalisers.
     affine: optional float32 CUDA [B, 3, 4] (one map per sample) or [B, 2, 3, 4] (index 0 CT and label, index 1 MR), the
-    F.affine_grid theta the resample reads on the device; padding_mode: "zeros" | "border", read only with `affine`.
+    F.affine_grid theta the resample reads on the device; padding_mode: "zeros" | "border", read only with `affine` or
+    `displacement`.  displacement: optional float32 CUDA [B, 3, gd, gh, gw], a displacement field in normalised output coordinates
+    on a control grid (micformer_amd/elastic.py), applied before `affine`; field_interpolation: "linear" | "cubic", read only with
+    `displacement`.
     -> (image fp16 [B, 2, D, H, W], label_map uint8 [B, D, H, W] | None, crop_indexes int32 [B, 3, 2])[, stats]."""
     D, H, W = _args.triple(size, "size")
     vals, nvals = _label_values(label_values)
     ct_mode, mr_mode = normalise.modes(normalisation)
     p_low, p_high = normalise.percentile_pair(percentiles)
+    if displacement is not None:
+        _elastic.typed(displacement)
     if affine is not None:
         _affine.typed(affine)
+    if displacement is not None and not isinstance(field_interpolation, str):
+        _elastic.interpolation(field_interpolation)                 # (its TypeError before the first ValueError)
+    if affine is not None or displacement is not None:
         pad = _affine.padding(padding_mode)
+    if displacement is not None:
+        interp = _elastic.interpolation(field_interpolation)
     samples = list(samples)
     if not samples:
         raise ValueError("load_batch needs at least one sample")
     B = len(samples)
-    if affine is not None:
-        per_modality = _affine.maps(affine, B)
+    per_modality = _affine.maps(affine, B) if affine is not None else 0
+    if displacement is not None:
+        gd, gh, gw = _elastic.fields(displacement, B)
     items = (LoaderSample * B)()
     device, has_label = None, None
     for b, smp in enumerate(samples):
@@ -147,8 +162,11 @@ def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, o
         crop = _args.out_tensor(out[2], "out crop_indexes", (B, 3, 2), torch.int32, device)
     if affine is not None and affine.device != device:
         raise ValueError(f"affine is on {affine.device}, the batch on {device}")
-    plain = affine is None and (ct_mode, mr_mode) == (normalise.MINMAX, normalise.MINMAX) and not return_stats
-    entry = "micf_volume_loader" + ("" if plain else "_norm" if affine is None else "_affine")
+    if displacement is not None and displacement.device != device:
+        raise ValueError(f"displacement is on {displacement.device}, the batch on {device}")
+    warped = affine is not None or displacement is not None
+    plain = not warped and (ct_mode, mr_mode) == (normalise.MINMAX, normalise.MINMAX) and not return_stats
+    entry = "micf_volume_loader" + ("" if plain else "_norm" if not warped else "_affine" if displacement is None else "_elastic")
     stats = torch.empty((B, 2, 2), dtype=torch.float64, device=device) if return_stats else None
     nbytes = _lib.query_bytes(entry + "_workspace", B)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
@@ -158,25 +176,38 @@ def load_batch(samples, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, o
     args += [ws.data_ptr(), nbytes, image.data_ptr(), None if label_map is None else label_map.data_ptr(), crop.data_ptr()]
     if not plain:
         args.append(None if stats is None else stats.data_ptr())
-    if affine is not None:
-        args += [affine.data_ptr(), per_modality, pad]
+    if warped:
+        args += [None if affine is None else affine.data_ptr(), per_modality, pad]
+    if displacement is not None:
+        args += [displacement.data_ptr(), gd, gh, gw, interp]
     _lib.call_on(device, entry, *args)
     return (image, label_map, crop, stats) if return_stats else (image, label_map, crop)
 
 
 def load_pair(ct, mr, ct_label=None, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, normalisation="minmax",
-              percentiles=(1, 99), return_stats=False, affine=None, padding_mode="zeros"):
+              percentiles=(1, 99), return_stats=False, displacement=None, field_interpolation="linear", affine=None,
+              padding_mode="zeros"):
     """One sample: -> (image fp16 [2, D, H, W], label_map uint8 [D, H, W] | None, crop_indexes int32 [3, 2])[, stats float64
-    [2, 2]].  affine: [3, 4] or [2, 3, 4]."""
+    [2, 2]].  affine: [3, 4] or [2, 3, 4]; displacement: [3, gd, gh, gw]."""
+    if displacement is not None:
+        _elastic.typed(displacement)
     if affine is not None:
         _affine.typed(affine)
-        if not isinstance(padding_mode, str):
-            _affine.padding(padding_mode)                            # (its TypeError before the first ValueError)
+    if displacement is not None and not isinstance(field_interpolation, str):
+        _elastic.interpolation(field_interpolation)                  # (the keywords' TypeErrors before the first ValueError)
+    if (affine is not None or displacement is not None) and not isinstance(padding_mode, str):
+        _affine.padding(padding_mode)
+    if displacement is not None:
+        if displacement.dim() != 4:
+            raise ValueError(f"displacement of load_pair must have shape [3, gd, gh, gw], got {list(displacement.shape)}")
+        displacement = displacement.unsqueeze(0)                     # (a view: the kernel reads the caller's tensor)
+    if affine is not None:
         if affine.dim() not in (2, 3):
             raise ValueError(f"affine of load_pair must have shape [3, 4] or [2, 3, 4], got {list(affine.shape)}")
         affine = affine.unsqueeze(0)                                 # (a view: the kernels read the caller's tensor)
     res = load_batch([(ct, mr, ct_label)], size=size, label_values=label_values, normalisation=normalisation,
-                     percentiles=percentiles, return_stats=return_stats, affine=affine, padding_mode=padding_mode)
+                     percentiles=percentiles, return_stats=return_stats, displacement=displacement,
+                     field_interpolation=field_interpolation, affine=affine, padding_mode=padding_mode)
     one = (res[0][0], None if res[1] is None else res[1][0], res[2][0])
     return one + (res[3][0],) if return_stats else one
 

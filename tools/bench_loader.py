@@ -3,6 +3,7 @@ one JSON line per batch size.
 
     python tools/bench_loader.py [--batches 1,4] [--min-seconds 0.5] [--no-cpu] [--normalisation minmax|zscore|percentile|CT,MR]
                                  [--affine [--padding-mode zeros|border]]
+                                 [--elastic [--field-grid N] [--field-interpolation linear|cubic]]
 
 ms_per_call: device events around >= min-seconds of calls after warm-up (the whole call: workspace zeroing, min/max, resize + label + crop,
 crop finish).  minmax_ms: the same call with a 1x1x1 target, i.e. the full read of the raw image volumes plus launch overheads;
@@ -20,6 +21,11 @@ affine_ms_per_call against plain_ms_per_call, affine_stats_ms (the 1x1x1-target 
 the map) and affine_resample_ms (the difference), plus grid_sample_ms: F.affine_grid + F.grid_sample (bilinear) on the already
 loaded float16 image of the batch with the same maps, the second resample a user would run today (the label would need a third).
 There is no bar; the raw-volume statistics pass should still dominate.
+--elastic times the same call with a drawn displacement field per sample (elastic.draw_elastic on an N^3 control grid, default 7,
+csrc/volume_elastic.hip: elastic_resample_kernel), composed with the drawn map when --affine is given too: elastic_ms_per_call next
+to the affine and plain calls, elastic_stats_ms / elastic_resample_ms as above, and dense_grid_sample_ms: F.grid_sample (bilinear)
+of the already loaded float16 image on a dense [B, 128, 128, 128, 3] grid (F.affine_grid of the maps, or of the identity, plus the
+field upsampled to one vector per voxel once, outside the timing), the second resample this replaces.
 """
 import argparse
 import json
@@ -74,6 +80,9 @@ def main():
     ap.add_argument("--normalisation", default="minmax", help="one mode for both channels, or CT,MR")
     ap.add_argument("--affine", action="store_true", help="also time the call with a drawn affine map per sample")
     ap.add_argument("--padding-mode", default="zeros", choices=["zeros", "border"])
+    ap.add_argument("--elastic", action="store_true", help="also time the call with a drawn displacement field per sample")
+    ap.add_argument("--field-grid", type=int, default=7, help="control points per axis of the drawn field")
+    ap.add_argument("--field-interpolation", default="cubic", choices=["linear", "cubic"])
     a = ap.parse_args()
     norm = tuple(a.normalisation.split(",")) if "," in a.normalisation else a.normalisation
     default = norm == "minmax"
@@ -126,6 +135,29 @@ def main():
             row.update({"padding_mode": a.padding_mode, "plain_ms_per_call": row["ms_per_call"], "affine_ms_per_call": round(at, 4),
                         "affine_stats_ms": round(ast, 4), "affine_resample_ms": round(at - ast, 4),
                         "affine_minus_plain_ms": round(at - total, 4), "grid_sample_ms": round(gs, 4)})
+        if a.elastic:
+            import torch.nn.functional as F
+            from micformer_amd import affine, elastic
+            grid = (a.field_grid,) * 3
+            spacing = (SIZE[0] - 1) / (a.field_grid - 1)
+            field = elastic.draw_elastic(B, size=SIZE, grid=grid, magnitude=min(5.0, 0.4 * spacing),
+                                         generator=torch.Generator().manual_seed(100 + B), device="cuda")
+            theta = affine.draw_affine(B, size=SIZE, generator=torch.Generator().manual_seed(B), device="cuda") if a.affine else None
+            ekw = dict(kw, displacement=field, field_interpolation=a.field_interpolation, affine=theta, padding_mode=a.padding_mode)
+            et, _ = timed(lambda: loader.load_batch(dev, size=SIZE, out=out, **ekw), a.min_seconds)
+            est, _ = timed(lambda: loader.load_batch(dev, size=(1, 1, 1), out=tiny, **ekw), a.min_seconds)
+            image = out[0].clone()
+            eye = torch.eye(3, 4, device="cuda").expand(B, 3, 4)
+            dense = F.interpolate(field, size=SIZE, mode="trilinear", align_corners=True).permute(0, 2, 3, 4, 1)
+            dense = (F.affine_grid(eye if theta is None else theta, image.shape, align_corners=False) + dense).to(image.dtype)
+            gs, _ = timed(lambda: F.grid_sample(image, dense, mode="bilinear", padding_mode=a.padding_mode, align_corners=False),
+                          a.min_seconds)
+            row.update({"padding_mode": a.padding_mode, "field_grid": list(grid), "field_interpolation": a.field_interpolation,
+                        "plain_ms_per_call": row["ms_per_call"], "elastic_ms_per_call": round(et, 4),
+                        "elastic_stats_ms": round(est, 4), "elastic_resample_ms": round(et - est, 4),
+                        "elastic_minus_plain_ms": round(et - total, 4), "dense_grid_sample_ms": round(gs, 4)})
+            if a.affine:
+                row["elastic_minus_affine_ms"] = round(et - row["affine_ms_per_call"], 4)
         print(json.dumps(row), flush=True)
 
 
