@@ -346,9 +346,14 @@ extern "C" int micf_conv3_bwd_data(const float* dy, int dy_layout, const float* 
 // reduce; shapes the MFMA kernel does not take run item by item through micf_conv3_bwd_weight with the same workspace.
 extern "C" int64_t micf_conv3_bwd_weight_grouped_workspace(int n, int B, int D, int H, int W, int N, int c1, int c2) {
   if (n <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0 || c1 < 0 || c2 < 0) return 0;
-  const int64_t one = conv3_wgradx_workspace(B, D, H, W, N, c1, c2);
-  const int64_t all = conv3_wgradx_workspace(B, D, H, W, N, c1, c2, n);
-  return all > one ? all : one;
+  // the launches take 12 items at a time and the last one the rest: the largest of every count that can occur (the plan splits
+  // fewer items over more d ranges, so the size is not monotonic in the count)
+  int64_t most = 0;
+  for (int m = 1; m <= n && m <= 12; ++m) {
+    const int64_t f = conv3_wgradx_workspace(B, D, H, W, N, c1, c2, m);
+    most = f > most ? f : most;
+  }
+  return most;
 }
 
 extern "C" int64_t micf_conv3_bwd_weight_workspace(int B, int D, int H, int W, int N, int c1, int c2) {

@@ -3,211 +3,52 @@
 //
 //   dW[n][c][tap] = sum_t dy[t, n] * in[t + off(tap), c]                 in = [x1 | x2], n < 16
 //
-// MFMA 16x16x4 fp32: rows i = 16 input channels, columns j = the 16 dy channels, k = 4 tokens.  A workgroup owns a slab of
-// 48 input channels x 27 taps = 81 (tap, channel tile) pairs -> 21 accumulator tiles (84 AGPRs) in each of its 4 waves,
-// and walks token tiles of 64 tokens: the input halo of the tile (the slab's 48 channels, voxel stride 52 floats: the four k
-// lanes land on banks 0/16/32/48, conflict-free) is staged in LDS once, the dy fragment of a 16-token group is 4 registers,
-// and every MFMA then costs exactly one 4-byte LDS read.  Partial slabs go to a workspace with coalesced 16-byte stores
-// and a second kernel sums them over the workgroups and scatters into the [N][Cin][27] layout (+=).
-// The LDS-tiled VALU kernel this replaces (conv3_wgrad.hip) reached 28 TFLOP/s at the 32^3 x 2 stage.
+// MFMA rows i = 16 input channels, columns j = the 16 dy channels, k = tokens.  A workgroup owns a slab of 48 input channels x
+// 27 taps = 81 (tap, channel tile) pairs -> 21 accumulator tiles (84 registers) in each of its 4 waves, an (h, w) footprint of 64
+// tokens of one sample and a contiguous range of its d planes (conv3_wgrad_plan.h holds that split and is shared with the host).
+// It MARCHES the range: the halo planes d - 1, d, d + 1 of the footprint sit in an LDS ring of three, a step commits the one new
+// plane d + 1 ((TH + 2) x (TW + 2) voxel rows of the slab's 48 channels) over the slot of plane d - 2, and two register sets run
+// ahead of the ring (planes d + 2 and d + 3 are in flight under the MFMAs of step d).  Planes -1 and D are zeros, a range never
+// crosses a sample, a range that starts inside a sample primes two planes.  What a thread moves of every plane is the same, so its
+// source addresses and LDS offsets are worked out once, before the march.  A tap is an offset on the centre voxel's address:
+// in-plane part fixed, plane part = the ring slot of d + kd - 1, which is wave-uniform and changes per step.
+//   * bf16 mode (the benched one, conv3_wgradx_b16_kernel): x and dy are rounded to bf16 (RNE) at the LDS write, token-major, and the
+//     fragments -- 8 tokens of one channel per lane -- are read with the transposing ds_read_b64_tr_b16; dbias sums the unrounded dy.
+//   * fp32 mode (the parity mode, conv3_wgradx_kernel): MFMA 16x16x4 fp32, voxel stride 52 floats, one 4-byte LDS read per MFMA.
+// Partial slabs go to a workspace with coalesced 16-byte stores (the float4 of a lane re-ordered so that the 16 of one quad of dy
+// channels are contiguous) and conv3_wgradx_reduce_kernel sums them in a fixed order and adds them into [N][Cin][27].
 #include <cstdlib>
 #include <mutex>
 
 #include "common.h"
+#include "conv3_wgrad_plan.h"
 #include "gemm_dma.h"
 
 namespace micf {
 
-constexpr int wCS = 48;                 // channels per slab (3 channel tiles): 67 KB of LDS, so a workgroup of the other stream fits beside it
-constexpr int wDS = 20;                 // LDS stride of a dy row (floats): the four lane groups' tokens are 80 floats = 16 banks apart
-constexpr int wXS = 52;                 // LDS voxel stride (floats): 4 * 52 = 208 = 16 (mod 64) -> the four k lanes hit disjoint banks
-constexpr int wPairs = 27 * (wCS / 16); // 81 (tap, channel tile) pairs per slab
-constexpr int wTPW = (wPairs + 3) / 4;  // 21 accumulator tiles per wave
-constexpr int wSlabFloats = 4 * wTPW * 256;   // partial slab of one workgroup in the workspace (21.5 K floats)
+namespace wgp = micf_wgrad;
 
-constexpr int kWgxItems = 12;           // layers of one shape per launch (blockIdx.z): the two modalities' offset convs of every
-                                        // depth slot a flush hands over (6 items at the six-slot stages)
+constexpr int wCS = wgp::kSlabChannels; // channels per slab (3 channel tiles)
+constexpr int wDS = 20;                 // fp32 mode: LDS stride of a dy row (floats): the four lane groups' tokens are 80 floats = 16 banks apart
+constexpr int wXS = 52;                 // fp32 mode: LDS voxel stride (floats): 4 * 52 = 208 = 16 (mod 64) -> the four k lanes hit disjoint banks
+constexpr int wPairs = wgp::kPairs;     // 81 (tap, channel tile) pairs per slab
+constexpr int wTPW = wgp::kTilesPerWave;   // 21 accumulator tiles per wave
+constexpr int wRSB = 104;               // bf16 mode: bytes per halo voxel row: 48 bf16 + 8 pad (26 dwords: the 4 token rows of a read are bank-disjoint)
+constexpr int wDYB = 40;                // bf16 mode: bytes per dy token row: 16 bf16 + 8 pad
+
+constexpr int kWgxItems = wgp::kMaxItems;   // layers of one shape per launch (blockIdx.y): the two modalities' offset convs of every
+                                            // depth slot a flush hands over (6 items at the six-slot stages)
 struct WgxArgs {
   const float* dy[kWgxItems];           // channels-last [T, 16]
   const float* x1[kWgxItems]; const float* x2[kWgxItems];
   int c1, c2;
-  float* ws;                            // [item][slabs][groups][wSlabFloats]
-  float* bias_ws;                       // [item][groups][16]  (slab 0 only) or nullptr
-  int B, D, H, W, tiles_d, tiles_h, tiles_w, tiles_per_group, groups, slabs, xcd_order;
+  float* ws;                            // wgp::slab_offset / wgp::bias_offset
+  int want_bias;
+  wgp::Plan plan;
 };
 
-// TW: tile extent along w (16 or 8).  Tile = 1 (d) x 64/TW (h) x TW (w) = 64 tokens; a token group is 16/TW h-rows x TW.
-template <int TW, bool BF16>
-__global__ void __launch_bounds__(256) conv3_wgradx_kernel(WgxArgs a) {
-  constexpr int CH = 16 / TW, TH = 64 / TW;
-  constexpr int HH = TH + 2, HW = TW + 2, HALO = 3 * HH * HW;
-  extern __shared__ __attribute__((aligned(16))) float Xs[];           // [HALO][wXS]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lr = lane >> 4;
-  // XCD-aware order: workgroups are dealt to the 8 XCDs round-robin by linear id; the tile ranges (consecutive d planes, whose
-  // halos overlap) handed to one XCD are made contiguous so the planes a workgroup shares with its neighbours hit that XCD's L2
-  int slab = blockIdx.x, group = blockIdx.y;
-  const int item = blockIdx.z;
-  if (a.xcd_order) {
-    const int L = gridDim.x * gridDim.y;
-    const int lin = slab + gridDim.x * group;
-    const int logical = (lin % 8) * (L / 8) + lin / 8;
-    slab = logical % gridDim.x;
-    group = logical / gridDim.x;
-  }
-  const float* __restrict__ a_dy = a.dy[item];
-  const float* __restrict__ a_x1 = a.x1[item];
-  const float* __restrict__ a_x2 = a.x2[item];
-  const int Cin = a.c1 + a.c2;
-  const int cbase = slab * wCS;
-  const int64_t DHW = (int64_t)a.D * a.H * a.W;
-
-  f32x4 acc[wTPW];
-#pragma unroll
-  for (int p = 0; p < wTPW; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float bsum = 0.f;                                                    // colsum(dy) partial of column li (wave 0 only)
-  int offs[wTPW];                                                      // LDS offset of (tap, channel tile) p of this wave
-#pragma unroll
-  for (int p = 0; p < wTPW; ++p) {
-    const int pair = min(wave * wTPW + p, wPairs - 1);                  // the 3 surplus tiles of wave 3 recompute the last pair
-    const int tap = pair / (wCS / 16), ct = pair % (wCS / 16);          // (never read back): no branch in the MFMA stream
-    const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
-    offs[p] = (((kd - 1) * HH + (kh - 1)) * HW + (kw - 1)) * wXS + ct * 16;
-  }
-
-  const int ntiles = a.B * a.tiles_d * a.tiles_h * a.tiles_w;
-  const int t_begin = group * a.tiles_per_group;
-  const int t_end = min(ntiles, t_begin + a.tiles_per_group);
-  // The halo and the dy rows of the NEXT tile are fetched into registers under the MFMAs of the current one (one workgroup per
-  // CU: nothing else hides the load latency) and committed to LDS after the barrier that ends the current tile.  The MFMA phase
-  // itself issues no global load (dy fragments come from LDS): loads return in order, one issued there would wait for the prefetch.
-  constexpr int NQ = HALO * (wCS / 4);
-  constexpr int NB = 16;
-  static_assert(NQ <= 256 * NB, "one batch per tile");
-  float* Dys = Xs + HALO * wXS;                                        // [64 tokens][wDS] dy of the tile
-  float4 v[NB], vdy;
-  auto fetch = [&](int tile) {
-    int q = tile;
-    const int tw = q % a.tiles_w; q /= a.tiles_w;
-    const int th = q % a.tiles_h; q /= a.tiles_h;
-    const int d0 = q % a.tiles_d; const int b = q / a.tiles_d;
-    const int h0 = th * TH, w0 = tw * TW;
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const int idx = u * 256 + tid;
-      v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx < NQ) {
-        const int hv = idx / (wCS / 4), g = idx % (wCS / 4);
-        const int hw = hv % HW, hh = (hv / HW) % HH, hd = hv / (HW * HH);
-        const int dd = d0 + hd - 1, yy = h0 + hh - 1, ww = w0 + hw - 1;
-        const int c = cbase + 4 * g;
-        if ((unsigned)dd < (unsigned)a.D && (unsigned)yy < (unsigned)a.H && (unsigned)ww < (unsigned)a.W && c < Cin) {
-          const int64_t tok = (int64_t)b * DHW + ((int64_t)dd * a.H + yy) * a.W + ww;
-          v[u] = c < a.c1 ? *reinterpret_cast<const float4*>(a_x1 + tok * a.c1 + c)
-                          : *reinterpret_cast<const float4*>(a_x2 + tok * a.c2 + (c - a.c1));
-        }
-      }
-    }
-    {
-      const int tk = tid >> 2, yy = h0 + tk / TW, ww = w0 + tk % TW;    // tile-local token tk = lh * TW + lw
-      vdy = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (yy < a.H && ww < a.W)
-        vdy = *reinterpret_cast<const float4*>(a_dy + ((int64_t)b * DHW + ((int64_t)d0 * a.H + yy) * a.W + ww) * 16 + 4 * (tid & 3));
-    }
-  };
-  if (t_begin < t_end) fetch(t_begin);
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    __syncthreads();                                                   // previous tile fully consumed
-    // ---- commit: HALO voxels x 12 float4 (channels cbase .. cbase+47 of [x1 | x2]) and the 64 x 16 dy rows
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const int idx = u * 256 + tid;
-      if (idx < NQ) *reinterpret_cast<float4*>(&Xs[(idx / (wCS / 4)) * wXS + 4 * (idx % (wCS / 4))]) = v[u];
-    }
-    *reinterpret_cast<float4*>(&Dys[(tid >> 2) * wDS + 4 * (tid & 3)]) = vdy;
-    // dy fragment of a 16-token group (k-permutation: in step s lane group lr supplies token j = 4*lr + s of the group)
-    auto load_dy = [&](int g, float (&bv)[4]) {
-#pragma unroll
-      for (int s = 0; s < 4; ++s) bv[s] = g < 4 ? Dys[(g * 16 + 4 * lr + s) * wDS + li] : 0.f;
-    };
-    __syncthreads();
-    if (tile + 1 < t_end) fetch(tile + 1);
-    float bv[4], bn[4];
-    load_dy(0, bv);
-
-    if constexpr (!BF16) {
-    // ---- 4 token groups of 16 tokens
-#pragma unroll 1
-    for (int g = 0; g < 4; ++g) {
-      load_dy(g + 1, bn);
-      int vox[4];
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int j = 4 * lr + s;
-        const int lh = g * CH + j / TW, lw = j % TW;
-        vox[s] = ((1 * HH + lh + 1) * HW + lw + 1) * wXS + li;          // centre voxel of the token, + channel li
-      }
-      if (a.bias_ws && wave == 0) bsum += bv[0] + bv[1] + bv[2] + bv[3];
-      // s outer / pair inner: consecutive MFMAs hit different accumulators (no back-to-back dependency on one tile)
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-#pragma unroll
-        for (int p = 0; p < wTPW; ++p) {
-          acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(Xs[vox[s] + offs[p]], bv[s], acc[p], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) bv[s] = bn[s];
-    }
-    } else {
-    // ---- bf16: k = 32 tokens per MFMA = two 16-token groups (lane group lr supplies tokens 4 lr + s of each)
-#pragma unroll 1
-    for (int g = 0; g < 4; g += 2) {
-      float b2[4];
-      load_dy(g + 1, b2);
-      load_dy(g + 2, bn);
-      int vox[8];
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        const int j = 4 * lr + (s & 3);
-        const int lh = (g + (s >> 2)) * CH + j / TW, lw = j % TW;
-        vox[s] = ((1 * HH + lh + 1) * HW + lw + 1) * wXS + li;
-      }
-      if (a.bias_ws && wave == 0) bsum += (bv[0] + bv[1] + bv[2] + bv[3]) + (b2[0] + b2[1] + b2[2] + b2[3]);
-      const bf16x8 bb = to_bf16x8(make_float4(bv[0], bv[1], bv[2], bv[3]), make_float4(b2[0], b2[1], b2[2], b2[3]));
-#pragma unroll
-      for (int p = 0; p < wTPW; ++p) {
-        const float* xp = Xs + offs[p];
-        const bf16x8 ba = to_bf16x8(make_float4(xp[vox[0]], xp[vox[1]], xp[vox[2]], xp[vox[3]]),
-                                    make_float4(xp[vox[4]], xp[vox[5]], xp[vox[6]], xp[vox[7]]));
-        acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ba, bb, acc[p], 0, 0, 0);
-      }
-#pragma unroll
-      for (int s = 0; s < 4; ++s) bv[s] = bn[s];
-    }
-    }
-  }
-  // ---- partial slab -> workspace: [(wave*TPW + p)][lane][4], 16-byte stores
-  float* out = a.ws + (((int64_t)item * a.slabs + slab) * a.groups + group) * wSlabFloats;
-#pragma unroll
-  for (int p = 0; p < wTPW; ++p)
-    *reinterpret_cast<float4*>(out + ((wave * wTPW + p) * 64 + lane) * 4) = make_float4(acc[p][0], acc[p][1], acc[p][2], acc[p][3]);
-  if (a.bias_ws && slab == 0 && wave == 0) {
-    bsum += __shfl_xor(bsum, 16, 64);
-    bsum += __shfl_xor(bsum, 32, 64);
-    if (lane < 16) a.bias_ws[((int64_t)item * a.groups + group) * 16 + lane] = bsum;
-  }
-}
-
-// ---- bf16 mode, round 3: the halo and the dy rows sit in LDS as bf16, token-major (no transposing staging), and the MFMA fragments
-// -- 8 tokens of one channel per lane -- are read with the transposing LDS read ds_read_b64_tr_b16: lanes 4 j .. 4 j + 3 of a 16-lane
-// group address token row j (8 bytes = 4 channels each), lane i receives column i.  The 4 rows of a read are ARBITRARY addresses,
-// so a tap is just a byte offset on every row address (whole voxel rows: no sub-row misalignment), and one (tap, channel tile)
-// costs 2 reads + 2 adds per MFMA where the fp32-staged kernel above pays 8 reads + 8 adds + 4 conversions (SQ counters put
-// that kernel at 58 % issue-busy on its one wave per SIMD: instruction-bound).  34 KB of LDS instead of 72: a workgroup of the
-// main chain fits beside it.  Same accumulator / workspace layout as above, same reduce kernel.
-constexpr int wRSB = 104;               // bytes per halo voxel row: 48 bf16 + 8 pad (26 dwords: the 4 token rows of a read are bank-disjoint)
-constexpr int wDYB = 40;                // bytes per dy token row: 16 bf16 + 8 pad
 typedef short s16x4x __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ bf16x8 tr_pair(unsigned a0, unsigned a1) {
   const s16x4x lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4x*)(uintptr_t)a0);
@@ -215,211 +56,333 @@ __device__ __forceinline__ bf16x8 tr_pair(unsigned a0, unsigned a1) {
   return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
-template <int TW>
-__global__ void __launch_bounds__(256) conv3_wgradx_b16_kernel(WgxArgs a) {
-  constexpr int TH = 64 / TW;
-  constexpr int HH = TH + 2, HW = TW + 2, HALO = 3 * HH * HW;
-  extern __shared__ __attribute__((aligned(16))) char smem[];          // Xh [HALO][wRSB] | Dy [64][wDYB]
+// LDS of one workgroup: the ring of 3 planes, then the dy rows of the step's 64 tokens
+template <int TW, bool BF16>
+constexpr int wgx_lds_bytes() {
+  constexpr int PL = (64 / TW + 2) * (TW + 2);
+  return BF16 ? 3 * PL * wRSB + 64 * wDYB : (int)sizeof(float) * (3 * PL * wXS + 64 * wDS);
+}
+
+// TW: footprint extent along w (16 or 8).  Footprint = 64/TW (h) x TW (w) = 64 tokens per plane.
+template <int TW, bool BF16>
+__device__ __forceinline__ void wgx_march(const WgxArgs& a, char* smem) {
+  constexpr int TH = 64 / TW, HH = TH + 2, HW = TW + 2;
+  constexpr int PL = HH * HW;                                          // voxel rows of one halo plane
+  constexpr int ROWB = BF16 ? wRSB : wXS * (int)sizeof(float);         // bytes per voxel row
+  constexpr int PLB = PL * ROWB;
+  constexpr int NQ = PL * (wCS / 4);                                   // float4 of one plane
+  constexpr int NB = (NQ + 255) / 256;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), li = lane & 15, lr = lane >> 4;
-  int slab = blockIdx.x, group = blockIdx.y;
-  const int item = blockIdx.z;
-  if (a.xcd_order) {
-    const int L = gridDim.x * gridDim.y;
-    const int lin = slab + gridDim.x * group;
-    const int logical = (lin % 8) * (L / 8) + lin / 8;
-    slab = logical % gridDim.x;
-    group = logical / gridDim.x;
-  }
+  const wgp::Unit un = wgp::decode(a.plan, blockIdx.x);
+  const int item = blockIdx.y;
   const float* __restrict__ a_dy = a.dy[item];
   const float* __restrict__ a_x1 = a.x1[item];
   const float* __restrict__ a_x2 = a.x2[item];
-  const int Cin = a.c1 + a.c2;
-  const int cbase = slab * wCS;
-  const int64_t DHW = (int64_t)a.D * a.H * a.W;
-  const unsigned xh = (unsigned)(uintptr_t)smem, dyl = xh + HALO * wRSB;
+  const int D = a.plan.D, H = a.plan.H, W = a.plan.W, Cin = a.c1 + a.c2;
+  const int cbase = un.slab * wCS, h0 = un.h0, w0 = un.w0;
+  const int64_t tok0 = (int64_t)un.b * D * H * W;                      // first token of the sample
+  const unsigned xh = (unsigned)(uintptr_t)smem, dyl = xh + 3 * PLB;
 
   f32x4 acc[wTPW];
 #pragma unroll
   for (int p = 0; p < wTPW; ++p) acc[p] = f32x4{0.f, 0.f, 0.f, 0.f};
-  int offs[wTPW];                                                      // byte offset of (tap, channel tile) p of this wave
+  // (tap, channel tile) p of this wave: the in-plane part of its offset from the centre voxel (bytes).  Its plane kd is one of
+  // two per wave: pairs run tap-major, so the wave's 21 pairs cross at most one multiple of 27.
+  int offs[wTPW];
 #pragma unroll
   for (int p = 0; p < wTPW; ++p) {
-    const int pair = min(wave * wTPW + p, wPairs - 1);
-    const int tap = pair / (wCS / 16), ct = pair % (wCS / 16);
-    const int kd = tap / 9, kh = (tap / 3) % 3, kw = tap % 3;
-    offs[p] = (((kd - 1) * HH + (kh - 1)) * HW + (kw - 1)) * wRSB + ct * 32;
+    const int pair = min(wave * wTPW + p, wPairs - 1);                  // the 3 surplus tiles of wave 3 recompute the last pair
+    const int tap = pair / (wCS / 16), ct = pair % (wCS / 16);          // (never read back): no branch in the MFMA stream
+    const int kh = (tap / 3) % 3, kw = tap % 3;
+    offs[p] = ((kh - 1) * HW + (kw - 1)) * ROWB + ct * (BF16 ? 32 : 64);
   }
-  // token t = 8 lr + 4 r + (li >> 2) of k-step ks (32 tokens = 32 / TW tile rows): its centre voxel row in the halo / its dy row
+  const int kd_a = (wave * wTPW) / 27, kd_b = min(kd_a + 1, 2);
+  const int kd_split = 27 * (kd_a + 1) - wave * wTPW;                   // pairs p < kd_split lie in plane kd_a, the others in kd_b
+
+  // bf16: token t = 8 lr + 4 r + (li >> 2) of k-step ks (32 tokens = 32 / TW rows): its centre voxel row in a plane / its dy row
   unsigned abase[2][2], bbase[2][2];
+  if constexpr (BF16) {
 #pragma unroll
-  for (int ks = 0; ks < 2; ++ks)
+    for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int t = 8 * lr + 4 * r + (li >> 2);
-      const int lh = ks * (32 / TW) + t / TW, lw = t % TW;
-      abase[ks][r] = xh + (unsigned)(((1 * HH + lh + 1) * HW + lw + 1) * wRSB + 8 * (li & 3));
-      bbase[ks][r] = dyl + (unsigned)((32 * ks + t) * wDYB + 8 * (li & 3));
-    }
+      for (int r = 0; r < 2; ++r) {
+        const int t = 8 * lr + 4 * r + (li >> 2);
+        const int lh = ks * (32 / TW) + t / TW, lw = t % TW;
+        abase[ks][r] = xh + (unsigned)(((lh + 1) * HW + lw + 1) * ROWB + 8 * (li & 3));
+        bbase[ks][r] = dyl + (unsigned)((32 * ks + t) * wDYB + 8 * (li & 3));
+      }
+  }
   float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);                         // column sums of dy (channels 4 (tid & 3) ..) over this thread's tokens
 
-  const int ntiles = a.B * a.tiles_d * a.tiles_h * a.tiles_w;
-  const int t_begin = group * a.tiles_per_group;
-  const int t_end = min(ntiles, t_begin + a.tiles_per_group);
-  constexpr int NQ = HALO * (wCS / 4);
-  constexpr int NB = 16;
-  static_assert(NQ <= 256 * NB, "one batch per tile");
-  float4 v[NB], vdy;
-  auto fetch = [&](int tile) {
-    int q = tile;
-    const int tw = q % a.tiles_w; q /= a.tiles_w;
-    const int th = q % a.tiles_h; q /= a.tiles_h;
-    const int d0 = q % a.tiles_d; const int b = q / a.tiles_d;
-    const int h0 = th * TH, w0 = tw * TW;
+  // What thread tid moves of EVERY plane is fixed for the whole march, so its addresses are worked out once: float4 u is voxel row
+  // hv = idx / 12 of the plane, channels cbase + 4 (idx % 12) .., idx = 256 u + tid.
+  const float* fsrc[NB];                                               // its address in plane 0 of the sample; nullptr: zeros (h / w border, c >= Cin, idx >= NQ)
+  int fstride[NB];                                                     // floats from one plane to the next in its source (x1 or x2)
+  unsigned fdst[NB];                                                   // its byte offset in a ring slot
+#pragma unroll
+  for (int u = 0; u < NB; ++u) {
+    const int idx = u * 256 + tid;
+    const int hv = idx / (wCS / 4), g = idx % (wCS / 4);
+    const int yy = h0 + hv / HW - 1, ww = w0 + hv % HW - 1;
+    const int c = cbase + 4 * g;
+    const bool first = c < a.c1;
+    const int cw = first ? a.c1 : a.c2;
+    const bool ok = idx < NQ && (unsigned)yy < (unsigned)H && (unsigned)ww < (unsigned)W && c < Cin;
+    fsrc[u] = ok ? (first ? a_x1 + c : a_x2 + (c - a.c1)) + (tok0 + (int64_t)yy * W + ww) * cw : nullptr;
+    fstride[u] = H * W * cw;
+    fdst[u] = (unsigned)(hv * ROWB + (BF16 ? 8 : 16) * g);
+  }
+  // plane dd of the footprint's halo -> registers (zeros for the planes -1 and D)
+  auto fetch = [&](int dd, float4 (&v)[NB]) {
+    const bool plane = (unsigned)dd < (unsigned)D;
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
-      const int idx = u * 256 + tid;
       v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx < NQ) {
-        const int hv = idx / (wCS / 4), g = idx % (wCS / 4);
-        const int hw = hv % HW, hh = (hv / HW) % HH, hd = hv / (HW * HH);
-        const int dd = d0 + hd - 1, yy = h0 + hh - 1, ww = w0 + hw - 1;
-        const int c = cbase + 4 * g;
-        if ((unsigned)dd < (unsigned)a.D && (unsigned)yy < (unsigned)a.H && (unsigned)ww < (unsigned)a.W && c < Cin) {
-          const int64_t tok = (int64_t)b * DHW + ((int64_t)dd * a.H + yy) * a.W + ww;
-          v[u] = c < a.c1 ? *reinterpret_cast<const float4*>(a_x1 + tok * a.c1 + c)
-                          : *reinterpret_cast<const float4*>(a_x2 + tok * a.c2 + (c - a.c1));
-        }
+      if (plane && fsrc[u]) v[u] = *reinterpret_cast<const float4*>(fsrc[u] + (int64_t)dd * fstride[u]);
+    }
+  };
+  auto commit = [&](int slot, const float4 (&v)[NB]) {
+    char* base = smem + slot * PLB;
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      if (u * 256 + tid < NQ) {
+        if constexpr (BF16) *reinterpret_cast<u32x2w*>(base + fdst[u]) = u32x2w{pack_bf16(v[u].x, v[u].y), pack_bf16(v[u].z, v[u].w)};
+        else *reinterpret_cast<float4*>(base + fdst[u]) = v[u];
       }
     }
-    const int tk = tid >> 2, yy = h0 + tk / TW, ww = w0 + tk % TW;      // tile-local token tk = lh * TW + lw
-    vdy = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (yy < a.H && ww < a.W)
-      vdy = *reinterpret_cast<const float4*>(a_dy + ((int64_t)b * DHW + ((int64_t)d0 * a.H + yy) * a.W + ww) * 16 + 4 * (tid & 3));
   };
-  typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
-  if (t_begin < t_end) fetch(t_begin);
-  for (int tile = t_begin; tile < t_end; ++tile) {
-    __syncthreads();                                                   // previous tile fully consumed
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-      const int idx = u * 256 + tid;
-      if (idx < NQ)
-        *reinterpret_cast<u32x2w*>(smem + (idx / (wCS / 4)) * wRSB + 8 * (idx % (wCS / 4))) = u32x2w{pack_bf16(v[u].x, v[u].y), pack_bf16(v[u].z, v[u].w)};
+  // dy of the 64 tokens of plane dd: thread tid holds channels 4 (tid & 3) .. of tile-local token tid >> 2 (= lh * TW + lw)
+  const float* dsrc = nullptr;
+  {
+    const int tk = tid >> 2, yy = h0 + tk / TW, ww = w0 + tk % TW;
+    if (yy < H && ww < W) dsrc = a_dy + (tok0 + (int64_t)yy * W + ww) * 16 + 4 * (tid & 3);
+  }
+  const int dstride = H * W * 16;
+  auto fetch_dy = [&](int dd) {
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (dsrc) r = *reinterpret_cast<const float4*>(dsrc + (int64_t)dd * dstride);
+    return r;
+  };
+
+  // ---- prime the ring with planes d0 - 1 and d0 (slot of plane d = d mod 3).  Two register sets run ahead of the ring: at step d
+  // one holds plane d + 1 and dy(d), which the step commits, the other plane d + 2 and dy(d + 1), still in flight; the set just
+  // committed is refilled with plane d + 3 and dy(d + 2).  All four fetches of the prologue are issued before the first wait.
+  float4 va[NB], vb[NB], dya, dyb = make_float4(0.f, 0.f, 0.f, 0.f);
+  int sc = un.d0 % 3;                                                  // slot of the centre plane d
+  {
+    float4 p0[NB], p1[NB];
+    fetch(un.d0 - 1, p0);
+    fetch(un.d0, p1);
+    fetch(un.d0 + 1, va);
+    dya = fetch_dy(un.d0);
+    if (un.d0 + 1 < un.d1) {
+      fetch(un.d0 + 2, vb);
+      dyb = fetch_dy(un.d0 + 1);
     }
-    *reinterpret_cast<u32x2w*>(smem + HALO * wRSB + (tid >> 2) * wDYB + 8 * (tid & 3)) = u32x2w{pack_bf16(vdy.x, vdy.y), pack_bf16(vdy.z, vdy.w)};
+    commit(sc == 0 ? 2 : sc - 1, p0);
+    commit(sc, p1);
+  }
+  auto step = [&](int d, float4 (&v)[NB], float4& vdy) {
+    const int sp = sc == 0 ? 2 : sc - 1, sn = sc == 2 ? 0 : sc + 1;     // slots of planes d - 1 and d + 1
+    __syncthreads();                                                   // step d - 1 fully consumed: slot sn (plane d - 2) and the dy rows are free
+    commit(sn, v);
+    if constexpr (BF16) *reinterpret_cast<u32x2w*>(smem + 3 * PLB + (tid >> 2) * wDYB + 8 * (tid & 3)) = u32x2w{pack_bf16(vdy.x, vdy.y), pack_bf16(vdy.z, vdy.w)};
+    else *reinterpret_cast<float4*>(smem + 3 * PLB + ((tid >> 2) * wDS + 4 * (tid & 3)) * (int)sizeof(float)) = vdy;
     bs.x += vdy.x; bs.y += vdy.y; bs.z += vdy.z; bs.w += vdy.w;
     __syncthreads();
-    if (tile + 1 < t_end) fetch(tile + 1);
+    // The set just committed is refilled under the MFMAs for the step after the next.  The MFMA phase itself issues no global
+    // load (dy fragments come from LDS): loads return in order, one issued there would wait for the planes in flight.
+    if (d + 2 < un.d1) {
+      fetch(d + 3, v);
+      vdy = fetch_dy(d + 2);
+    }
+    const int plane_a = (kd_a == 0 ? sp : kd_a == 1 ? sc : sn) * PLB, plane_b = (kd_b == 1 ? sc : sn) * PLB;   // ring slots of d + kd - 1
+
+    if constexpr (BF16) {
+      // 2 k-steps x 21 pairs in 6 batches of 7: the fragments of batch i + 1 are read while the MFMAs of batch i run (two
+      // register sets; LDS reads return in order, so a batch waits only for its own)
+      constexpr int G = 7, NBAT = 2 * (wTPW / G);
+      static_assert(wTPW % G == 0 && NBAT % 2 == 0, "batches of G pairs, two sets");
+      auto read_batch = [&](int bi, bf16x8 (&f)[G]) {
+        const int ks = bi / (wTPW / G), p0 = (bi % (wTPW / G)) * G;
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const bf16x8 bb = tr_pair(bbase[ks][0], bbase[ks][1]);
+        for (int i = 0; i < G; ++i) {
+          const int o = offs[p0 + i] + (p0 + i < kd_split ? plane_a : plane_b);
+          f[i] = tr_pair(abase[ks][0] + o, abase[ks][1] + o);
+        }
+      };
+      const bf16x8 bb[2] = {tr_pair(bbase[0][0], bbase[0][1]), tr_pair(bbase[1][0], bbase[1][1])};
+      auto mfma_batch = [&](int bi, const bf16x8 (&f)[G]) {
+        const int ks = bi / (wTPW / G), p0 = (bi % (wTPW / G)) * G;
 #pragma unroll
-      for (int p = 0; p < wTPW; ++p) {
-        const bf16x8 ba = tr_pair(abase[ks][0] + offs[p], abase[ks][1] + offs[p]);
-        acc[p] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ba, bb, acc[p], 0, 0, 0);
+        for (int i = 0; i < G; ++i) acc[p0 + i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[i], bb[ks], acc[p0 + i], 0, 0, 0);
+      };
+      bf16x8 f0[G], f1[G];
+      read_batch(0, f0);
+#pragma unroll
+      for (int bi = 0; bi < NBAT; bi += 2) {
+        read_batch(bi + 1, f1);
+        mfma_batch(bi, f0);
+        if (bi + 2 < NBAT) read_batch(bi + 2, f0);
+        mfma_batch(bi + 1, f1);
+      }
+    } else {
+      constexpr int CH = 16 / TW;
+      const float* Xs = reinterpret_cast<const float*>(smem);
+      const float* Dys = reinterpret_cast<const float*>(smem + 3 * PLB);
+      // dy fragment of a 16-token group (k-permutation: in step s lane group lr supplies token j = 4*lr + s of the group)
+      auto load_dy = [&](int g, float (&bv)[4]) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) bv[s] = g < 4 ? Dys[(g * 16 + 4 * lr + s) * wDS + li] : 0.f;
+      };
+      float bv[4], bn[4];
+      load_dy(0, bv);
+      // ---- 4 token groups of 16 tokens
+#pragma unroll 1
+      for (int g = 0; g < 4; ++g) {
+        load_dy(g + 1, bn);
+        int vox[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int j = 4 * lr + s;
+          const int lh = g * CH + j / TW, lw = j % TW;
+          vox[s] = ((lh + 1) * HW + lw + 1) * wXS + li;                // centre voxel of the token in a plane, + channel li
+        }
+        // s outer / pair inner: consecutive MFMAs hit different accumulators (no back-to-back dependency on one tile)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+#pragma unroll
+          for (int p = 0; p < wTPW; ++p) {
+            const int o = (offs[p] + (p < kd_split ? plane_a : plane_b)) >> 2;
+            acc[p] = __builtin_amdgcn_mfma_f32_16x16x4f32(Xs[vox[s] + o], bv[s], acc[p], 0, 0, 0);
+          }
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s) bv[s] = bn[s];
       }
     }
+    sc = sn;
+  };
+  for (int d = un.d0; d < un.d1; d += 2) {
+    step(d, va, dya);
+    if (d + 1 < un.d1) step(d + 1, vb, dyb);
   }
-  // ---- partial slab -> workspace: [(wave*TPW + p)][lane][4], 16-byte stores
-  float* out = a.ws + (((int64_t)item * a.slabs + slab) * a.groups + group) * wSlabFloats;
+  // ---- partial slab -> workspace: chunk (wave*TPW + p) of 64 float4, lane (n = li, channel quad lr) at n-quad major position:
+  // 16-byte stores, 1 KiB per wave instruction
+  float* out = a.ws + wgp::slab_offset(a.plan, item, un.slab, un.part);
+  const int pos = (li >> 2) * 16 + lr * 4 + (li & 3);
 #pragma unroll
   for (int p = 0; p < wTPW; ++p)
-    *reinterpret_cast<float4*>(out + ((wave * wTPW + p) * 64 + lane) * 4) = make_float4(acc[p][0], acc[p][1], acc[p][2], acc[p][3]);
-  if (a.bias_ws && slab == 0) {                                        // column sums of dy: over the lanes of one channel quad, then the waves
+    *reinterpret_cast<float4*>(out + ((wave * wTPW + p) * 64 + pos) * 4) = make_float4(acc[p][0], acc[p][1], acc[p][2], acc[p][3]);
+  if (a.want_bias && un.slab == 0) {                                   // column sums of dy: over the lanes of one channel quad, then the waves
 #pragma unroll
-    for (int d = 4; d < 64; d <<= 1) {
-      bs.x += __shfl_xor(bs.x, d, 64); bs.y += __shfl_xor(bs.y, d, 64); bs.z += __shfl_xor(bs.z, d, 64); bs.w += __shfl_xor(bs.w, d, 64);
+    for (int m = 4; m < 64; m <<= 1) {
+      bs.x += __shfl_xor(bs.x, m, 64); bs.y += __shfl_xor(bs.y, m, 64); bs.z += __shfl_xor(bs.z, m, 64); bs.w += __shfl_xor(bs.w, m, 64);
     }
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);
     if (lane < 4) *reinterpret_cast<float4*>(red + (wave * 4 + lane) * 4) = bs;
     __syncthreads();
-    if (tid < 16) a.bias_ws[((int64_t)item * a.groups + group) * 16 + tid] = red[tid] + red[16 + tid] + red[32 + tid] + red[48 + tid];
+    if (tid < 16) a.ws[wgp::bias_offset(a.plan, item, un.part) + tid] = red[tid] + red[16 + tid] + red[32 + tid] + red[48 + tid];
   }
 }
 
-// dw[n][c][tap] += sum over the groups' partial slabs;  dbias[n] += sum of the groups' column sums.
-// Block = 64 slab elements x 4 slices of the group range (independent loads, unrolled), combined through LDS.
+template <int TW>
+__global__ void __launch_bounds__(256) conv3_wgradx_kernel(WgxArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char wgx_smem[];
+  wgx_march<TW, false>(a, wgx_smem);
+}
+
+template <int TW>
+__global__ void __launch_bounds__(256, 2) conv3_wgradx_b16_kernel(WgxArgs a) {   // two workgroups per CU: at most 256 registers
+  extern __shared__ __attribute__((aligned(16))) char wgx_smem[];
+  wgx_march<TW, true>(a, wgx_smem);
+}
+
+// dw[n][c][tap] += sum over the parts' partial slabs;  dbias[n] += sum of the parts' column sums.  No atomics, one owner per
+// element and a fixed order of summation (part 0, 1, 2, ... in one thread): two runs are bit-identical.
+// A block owns, of one (item, slab, channel tile), a quad of dy channels: per (part, tap) 16 consecutive float4 of the slab (the
+// marching kernel stores them n-quad major), 27 x 16 = 432 columns, one per thread.  A thread streams its column over the parts
+// with up to 16 independent 16-byte loads in flight and no exchange with any other thread; the sums are then turned through LDS
+// into the block's [4 n][16 c][27 taps] -- per n one contiguous run of 432 floats of dw -- which is read, added and written back
+// in address order.
 struct WgxOut { float* dw[kWgxItems]; float* dbias[kWgxItems]; };
-__global__ void __launch_bounds__(256) conv3_wgradx_reduce_kernel(const float* __restrict__ ws_all, const float* __restrict__ bias_all,
-                                                                  WgxOut o, int Cin, int slabs, int groups) {
-  __shared__ float red[256];
+constexpr int kReduceThreads = 448;                                    // 7 waves: 432 columns
+__global__ void __launch_bounds__(kReduceThreads) conv3_wgradx_reduce_kernel(const float* __restrict__ ws, WgxOut o, int want_bias, wgp::Plan plan) {
+  __shared__ float4 red[27][16];
+  const int tid = threadIdx.x;
   const int item = blockIdx.y;
-  const float* __restrict__ ws = ws_all + (int64_t)item * slabs * groups * wSlabFloats;
-  const float* __restrict__ bias_ws = bias_all ? bias_all + (int64_t)item * groups * 16 : nullptr;
-  float* __restrict__ dw = o.dw[item];
-  float* __restrict__ dbias = o.dbias[item];
-  const int el = threadIdx.x & 63, slice = threadIdx.x >> 6;
-  const int64_t id = (int64_t)blockIdx.x * 64 + el;
-  const int64_t per_slab = (int64_t)wPairs * 256;
-  const bool main = id < per_slab * slabs;
-  const bool bias = !main && bias_ws && dbias && id < per_slab * slabs + 16;
-  float acc = 0.f;
-  int slab = 0, e = 0;
-  if (main) {
-    slab = (int)(id / per_slab);
-    e = (int)(id % per_slab);
-    const float* p = ws + (int64_t)slab * groups * wSlabFloats + e;
-    int g = slice;
-    for (; g + 28 < groups; g += 32) {
-      float v[8];
+  int q = blockIdx.x;
+  const int nq = q % 4; q /= 4;
+  const int ct = q % (wCS / 16);
+  const int slab = q / (wCS / 16);
+  const int parts = plan.parts, Cin = plan.Cin;
+  if (tid < 27 * 16) {
+    const int tap = tid >> 4, col = tid & 15;
+    constexpr int64_t STEP = wgp::kSlabFloats / 4;                     // float4 between the slabs of consecutive parts
+    const float4* __restrict__ src = reinterpret_cast<const float4*>(ws + wgp::slab_offset(plan, item, slab, 0)) + ((tap * (wCS / 16) + ct) * 64 + nq * 16 + col);
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    int part = 0;
+#pragma unroll 1
+    for (; part + 16 <= parts; part += 16) {
+      float4 v[16];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(g + 4 * u) * wSlabFloats];
+      for (int u = 0; u < 16; ++u) v[u] = src[(part + u) * STEP];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) acc += v[u];
+      for (int u = 0; u < 16; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
     }
-    for (; g < groups; g += 4) acc += p[(int64_t)g * wSlabFloats];
-  } else if (bias) {
-    const int n = (int)(id - per_slab * slabs);
-    for (int g = slice; g < groups; g += 4) acc += bias_ws[g * 16 + n];
+#pragma unroll 1
+    for (; part + 8 <= parts; part += 8) {
+      float4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = src[(part + u) * STEP];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { acc.x += v[u].x; acc.y += v[u].y; acc.z += v[u].z; acc.w += v[u].w; }
+    }
+    for (; part < parts; ++part) {
+      const float4 v = src[part * STEP];
+      acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    red[tap][col] = acc;
   }
-  red[threadIdx.x] = acc;
   __syncthreads();
-  if (slice != 0) return;
-  acc = red[el] + red[64 + el] + red[128 + el] + red[192 + el];
-  if (main) {
-    const int pair = e >> 8, lane = (e >> 2) & 63, v = e & 3;
-    const int tap = pair / (wCS / 16), ct = pair % (wCS / 16);
-    const int n = lane & 15, c = slab * wCS + ct * 16 + 4 * (lane >> 4) + v;
-    if (c < Cin) dw[((int64_t)n * Cin + c) * 27 + tap] += acc;
-  } else if (bias) {
-    dbias[(int)(id - per_slab * slabs)] += acc;
+  float* __restrict__ dw = o.dw[item];
+  const int c0 = slab * wCS + ct * 16;                                  // first of the block's 16 channels
+  const float* redf = reinterpret_cast<const float*>(&red[0][0]);
+  for (int e = tid; e < 4 * 16 * 27; e += kReduceThreads) {             // e = (j * 16 + cc) * 27 + tap: address order within the run of n = 4 nq + j
+    const int j = e / (16 * 27), rem = e % (16 * 27);
+    const int cc = rem / 27, tap = rem % 27;
+    if (c0 + cc < Cin) dw[((int64_t)(nq * 4 + j) * Cin + c0 + cc) * 27 + tap] += redf[((tap * 16) + (cc >> 2) * 4 + j) * 4 + (cc & 3)];
   }
-}
-
-struct WgxPlan { int slabs, groups, tiles_per_group, tw; int64_t floats; };
-
-static WgxPlan wgx_plan(int B, int D, int H, int W, int Cin, int items = 1) {
-  WgxPlan p;
-  p.tw = W >= 12 ? 16 : 8;
-  const int th = 64 / p.tw;
-  const int ntiles = B * D * ((H + th - 1) / th) * ((W + p.tw - 1) / p.tw);
-  p.slabs = (Cin + wCS - 1) / wCS;
-  constexpr int wg_target = 256;
-  int groups = (wg_target + p.slabs * items - 1) / (p.slabs * items);   // ~one workgroup per CU over all items
-  if (groups < 4) groups = 4 < ntiles ? 4 : ntiles;
-  if (groups > ntiles) groups = ntiles;
-  p.tiles_per_group = (ntiles + groups - 1) / groups;
-  p.groups = (ntiles + p.tiles_per_group - 1) / p.tiles_per_group;
-  p.floats = (int64_t)p.slabs * p.groups * wSlabFloats + (int64_t)p.groups * 16;
-  return p;
+  float* __restrict__ dbias = o.dbias[item];
+  if (want_bias && dbias && slab == 0 && ct == 0 && tid < 64) {         // dbias of the block's n quad: lane = n x 16 part slices
+    const float* __restrict__ b = ws + wgp::bias_offset(plan, item, 0) + nq * 4 + (tid & 3);
+    float s = 0.f;
+    for (int part = tid >> 2; part < parts; part += 16) s += b[(int64_t)part * 16];
+#pragma unroll
+    for (int m = 4; m < 64; m <<= 1) s += __shfl_xor(s, m, 64);
+    if (tid < 4) dbias[nq * 4 + tid] += s;
+  }
 }
 
 int64_t conv3_wgradx_workspace(int B, int D, int H, int W, int N, int c1, int c2, int items) {
-  if (N != 16 || W < 4 || (c1 & 3) || (c2 & 3) || items < 1 || items > kWgxItems) return 0;   // (W = 4: masked 8-wide tiles)
-  return wgx_plan(B, D, H, W, c1 + c2, items).floats * items;
+  if (N != 16 || W < 4 || (c1 & 3) || (c2 & 3) || c1 + c2 <= 0 || items < 1 || items > kWgxItems) return 0;   // (W = 4: masked 8-wide footprints)
+  return wgp::workspace_floats(wgp::make_plan(B, D, H, W, c1 + c2, items));
 }
 
 // MICF_EUNSUPPORTED when the shape / workspace is outside what this kernel covers (caller falls back).
-// n items of ONE shape per launch (blockIdx.z): dy / x1 / x2 / dw / dbias per item.
+// n items of ONE shape per launch (blockIdx.y): dy / x1 / x2 / dw / dbias per item.
 int conv3_wgradx_items(const float* const* dy, const float* const* x1, const float* const* x2, float* const* dw, float* const* dbias,
                        int n, int c1, int c2, int B, int D, int H, int W, int N, float* ws, int64_t ws_floats, hipStream_t stream,
                        int dtype) {
   const int64_t need = conv3_wgradx_workspace(B, D, H, W, N, c1, c2, n);
   if (need == 0 || !ws || ws_floats < need || !aligned16(ws)) return MICF_EUNSUPPORTED;
-  const WgxPlan p = wgx_plan(B, D, H, W, c1 + c2, n);
   WgxArgs a{};
   WgxOut o{};
+  a.plan = wgp::make_plan(B, D, H, W, c1 + c2, n);
+  const wgp::Plan& p = a.plan;
+  const int cmax = c1 > c2 ? c1 : c2;
+  if ((int64_t)p.slabs * p.parts > 0x7fffffffll || (int64_t)H * W * (cmax > 16 ? cmax : 16) > 0x7fffffffll) return MICF_EUNSUPPORTED;   // (plane strides are ints)
   bool any_bias = false;
   for (int i = 0; i < n; ++i) {
     if (!dy[i] || !x1[i] || !dw[i] || !aligned16(dy[i]) || !aligned16(x1[i]) || (x2 && x2[i] && !aligned16(x2[i]))) return MICF_EUNSUPPORTED;
@@ -428,33 +391,23 @@ int conv3_wgradx_items(const float* const* dy, const float* const* x1, const flo
     any_bias = any_bias || o.dbias[i];
   }
   a.c1 = c1; a.c2 = c2;
-  a.ws = ws; a.bias_ws = any_bias ? ws + (int64_t)n * p.slabs * p.groups * wSlabFloats : nullptr;
-  a.B = B; a.D = D; a.H = H; a.W = W;
-  const int th = 64 / p.tw;
-  a.tiles_d = D; a.tiles_h = (H + th - 1) / th; a.tiles_w = (W + p.tw - 1) / p.tw;
-  a.tiles_per_group = p.tiles_per_group; a.groups = p.groups; a.slabs = p.slabs;
-  a.xcd_order = ((p.slabs * p.groups) % 8 == 0) ? 1 : 0;   // XCD-contiguous tile ranges
+  a.ws = ws; a.want_bias = any_bias ? 1 : 0;
   static std::once_flag attr_once;       // > 64 KiB of dynamic LDS needs the opt-in once per process
   std::call_once(attr_once, [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_wgradx_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_wgradx_kernel<8, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_wgradx_b16_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_wgradx_b16_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_wgradx_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_wgradx_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
   });
-  const dim3 grid(p.slabs, p.groups, n);
+  const dim3 grid(wgp::grid_x(p), n);
+  const bool b16 = dtype == MICF_DTYPE_BF16;
   if (p.tw == 16) {
-    constexpr int HALO = 3 * (4 + 2) * (16 + 2);
-    if (dtype == MICF_DTYPE_BF16) hipLaunchKernelGGL((conv3_wgradx_b16_kernel<16>), grid, dim3(256), HALO * wRSB + 64 * wDYB, stream, a);
-    else hipLaunchKernelGGL((conv3_wgradx_kernel<16, false>), grid, dim3(256), sizeof(float) * (HALO * wXS + 64 * wDS), stream, a);
+    if (b16) hipLaunchKernelGGL((conv3_wgradx_b16_kernel<16>), grid, dim3(256), (wgx_lds_bytes<16, true>()), stream, a);
+    else hipLaunchKernelGGL((conv3_wgradx_kernel<16>), grid, dim3(256), (wgx_lds_bytes<16, false>()), stream, a);
   } else {
-    constexpr int HALO = 3 * (8 + 2) * (8 + 2);
-    if (dtype == MICF_DTYPE_BF16) hipLaunchKernelGGL((conv3_wgradx_b16_kernel<8>), grid, dim3(256), HALO * wRSB + 64 * wDYB, stream, a);
-    else hipLaunchKernelGGL((conv3_wgradx_kernel<8, false>), grid, dim3(256), sizeof(float) * (HALO * wXS + 64 * wDS), stream, a);
+    if (b16) hipLaunchKernelGGL((conv3_wgradx_b16_kernel<8>), grid, dim3(256), (wgx_lds_bytes<8, true>()), stream, a);
+    else hipLaunchKernelGGL((conv3_wgradx_kernel<8>), grid, dim3(256), (wgx_lds_bytes<8, false>()), stream, a);
   }
   if (hipGetLastError() != hipSuccess) return MICF_ELAUNCH;
-  const int64_t ne = (int64_t)wPairs * 256 * p.slabs + 16;
-  hipLaunchKernelGGL(conv3_wgradx_reduce_kernel, dim3((unsigned)((ne + 63) / 64), n), dim3(256), 0, stream, ws, a.bias_ws, o,
-                     c1 + c2, p.slabs, p.groups);
+  hipLaunchKernelGGL(conv3_wgradx_reduce_kernel, dim3(p.slabs * (wCS / 16) * 4, n), dim3(kReduceThreads), 0, stream, ws, o, a.want_bias, p);
   return hipGetLastError() == hipSuccess ? MICF_OK : MICF_ELAUNCH;
 }
 
