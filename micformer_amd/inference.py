@@ -6,6 +6,14 @@ scan interval int(roi * (1 - overlap)) per axis, ceil((L - roi) / interval) + 1 
 symmetric zero padding when the image is smaller than the ROI, constant importance map, output = sum(pred) / count in fp32.
 The referee is oracle/micformer_ref.py::sliding_window_inference (parity with MONAI itself is UNPINNED, see DESIGN.md).
 
+mode="gaussian" (nnU-Net's default blending) weights every window with the separable Gaussian importance map of blend.py:
+out[b, k, v] = sum_i w_i(v) p_i[k, v] / sum_i w_i(v) over the windows i that cover v, in the order they are enumerated here (z, y, x,
+then b).  It always takes the generic path -- predictor(win), then one plain read-modify-write launch per window
+(csrc/sw_blend.hip, no float atomics) -- so for the same predictions its result is bit-identical from run to run and for every
+sw_batch_size.  The map is
+this library's definition (blend.py); parity with MONAI's compute_importance_map is UNPINNED as well, the referee is
+tests/sw_blend_ref.py.
+
 The full-volume fp32 accumulator (8 x 512 x 512 x 256 = 2.1 GB for BASELINE config 5) and the visit counts stay in HBM; window
 crops, the accumulate and the final divide are HIP kernels (csrc/misc.hip); the predictor sees `sw_batch_size` windows per
 call -- the network is batch-independent, so any sw_batch_size gives the same result and large ones fill the GPU better.
@@ -14,8 +22,9 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, blend
 from ._lib import call, f32
+from .blend import importance_map  # noqa: F401  (public: the map sliding_window_inference applies)
 
 
 FUSE_ACCUMULATE = True
@@ -120,16 +129,21 @@ class GraphedPredictor:
         graph.replay()
 
 
-def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.5, mode="constant", *, graph=False,
-                             autocast=False):
+def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.5, mode="constant", sigma_scale=0.125, *,
+                             graph=False, autocast=False):
     """inputs (B, C, D, H, W) on the GPU -> (B, K, D, H, W) fp32, K = the predictor's output channels.
+    mode "constant" (MONAI's default: every voxel of a window weighs 1) or "gaussian" (blend.importance_map: sigma_scale, a positive
+    float or one per axis, times the roi size is the Gaussian's sigma; ignored for "constant").  The Gaussian mode calls
+    `predictor(win)` also for a Head that offers the fused accumulate epilogue, and for the same predictions it is bit-identical from
+    run to run and for every sw_batch_size; parity of its map with MONAI's is UNPINNED (blend.py states the definition).
     graph=True wraps the predictor in a GraphedPredictor (pass your own instance as `predictor` to reuse it across volumes).
     autocast=True runs the predictor with bf16 matrix-core operands -- this library's counterpart of the
     `torch.cuda.amp.autocast()` the reference wraps the call in (utils.py:236-238; fp16 there)."""
     if graph and not isinstance(predictor, GraphedPredictor):
         predictor = GraphedPredictor(predictor)
-    if mode != "constant":
-        raise NotImplementedError("only MONAI's default mode='constant' (what utils.py:228-234 uses) is implemented")
+    gaussian = blend.check_mode(mode) == "gaussian"
+    if gaussian:
+        blend.sigma_scales(sigma_scale)
     if inputs.dim() != 5 or not inputs.is_cuda:
         raise ValueError("sliding_window_inference expects a (B, C, D, H, W) CUDA (ROCm) tensor")
     if isinstance(roi_size, int):
@@ -151,8 +165,10 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     # adds its logits straight into the volume accumulator at the window origins and bumps the visit counts in its last launch --
     # no [n, K, roi] prediction tensor, no accumulate launch.  Needs roi dims that the patch size divides (else the model pads).
     base = predictor.predictor if isinstance(predictor, GraphedPredictor) else predictor
-    fused = FUSE_ACCUMULATE and hasattr(base, "forward_accumulate") and hasattr(base, "out_conv") \
+    fused = not gaussian and FUSE_ACCUMULATE and hasattr(base, "forward_accumulate") and hasattr(base, "out_conv") \
         and getattr(base, "can_accumulate", lambda roi: False)((rd, rh, rw))      # (else: the generic crop / predict / accumulate path)
+    if gaussian:
+        taps, floor = blend.device_taps((rd, rh, rw), sigma_scale, x.device)
     with torch.no_grad():
         if fused:
             K = base.out_conv.out_channels
@@ -197,7 +213,10 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
                 K = pred.shape[1]
                 out = ops.zero_(torch.empty((B, K, Dp, Hp, Wp), dtype=torch.float32, device=x.device))
                 count = ops.zero_(torch.empty((B, Dp, Hp, Wp), dtype=torch.float32, device=x.device))
-            ops.sw_accumulate_batch(pred, out, count, chunk)                  # ONE launch adds it into the volume accumulator
+            if gaussian:
+                blend.accumulate(pred, out, count, chunk, taps, floor)       # one launch per window, in order: `count` is sum(w)
+            else:
+                ops.sw_accumulate_batch(pred, out, count, chunk)              # ONE launch adds it into the volume accumulator
         for b in range(B):
             call("micf_sw_normalize", f32(out[b]), f32(count[b]), K, V)
         if fused and cached:
