@@ -164,12 +164,21 @@ def _mode(value, table, what):
     return table[value]
 
 
-def sample_patches(samples, indexes, draws, patch_size=(128, 128, 128), padding_mode="zeros", pad_class=0, clamp="both", out=None):
-    """indexes: index_scans' result for these samples.  Each index is checked against its sample by shape, dtypes and device;
-    label values, normalisation and percentiles, which a sample does not carry, are checked for agreement across the batch's
-    indexes (ValueError either way);
-    draws: float32 CUDA [B, 6], read on the device.  out: optional preallocated (image, label_map | None, origins, picked).
-    -> (image fp16 [B, 2, Pd, Ph, Pw], label_map uint8 [B, Pd, Ph, Pw] | None, origins int32 [B, 3], picked int32 [B, 4])."""
+def _typed(padding_mode, pad_class, clamp, draws):
+    """The TypeError half of sample_patches' keyword checks, for a caller (patch_warp) that raises every TypeError of its own
+    keywords before the first ValueError."""
+    for value, table, what in ((padding_mode, PADDING_MODES, "padding_mode"), (clamp, CLAMPS, "clamp")):
+        if not isinstance(value, str):
+            _mode(value, table, what)
+    if isinstance(pad_class, bool) or not isinstance(pad_class, int):
+        raise TypeError(f"pad_class must be an integer, got {type(pad_class).__name__}")
+    if not isinstance(draws, torch.Tensor) or draws.dtype != torch.float32:
+        raise TypeError("draws must be a float32 tensor")
+
+
+def _prepare(samples, indexes, draws, patch_size, padding_mode, pad_class, clamp, out, what="sample_patches"):
+    """Every check of sample_patches and the allocation of its outputs.  -> (the leading arguments of micf_patch_sample up to
+    `picked`, in order; the four outputs; device; B; what must stay alive until the call returns)."""
     Pd, Ph, Pw = _args.triple(patch_size, "patch_size")
     pad = _mode(padding_mode, PADDING_MODES, "padding_mode")
     clamp_mode = _mode(clamp, CLAMPS, "clamp")
@@ -179,7 +188,7 @@ def sample_patches(samples, indexes, draws, patch_size=(128, 128, 128), padding_
         raise ValueError(f"pad_class must lie in 0..255, got {pad_class}")
     if not isinstance(draws, torch.Tensor) or draws.dtype != torch.float32:
         raise TypeError("draws must be a float32 tensor")
-    items, device, has_label, meta = _describe(samples, "sample_patches")
+    items, device, has_label, meta = _describe(samples, what)
     B = len(meta)
     indexes = list(indexes)
     if len(indexes) != B:
@@ -214,19 +223,41 @@ def sample_patches(samples, indexes, draws, patch_size=(128, 128, 128), padding_
         picked = _args.out_tensor(out[3], "out picked", (B, 4), torch.int32, device)
     vals = _args.int32_array(list(indexes[0].label_values))
     ptrs, sizes = _index_arrays(indexes)
-    _lib.call_on(device, "micf_patch_sample", ctypes.addressof(items), B, ctypes.addressof(ptrs), ctypes.addressof(sizes),
-                 ctypes.addressof(vals), len(indexes[0].label_values), draws.data_ptr(), Pd, Ph, Pw, pad, pad_class, clamp_mode,
-                 image.data_ptr(), None if label_map is None else label_map.data_ptr(), origins.data_ptr(), picked.data_ptr())
-    return image, label_map, origins, picked
+    args = (ctypes.addressof(items), B, ctypes.addressof(ptrs), ctypes.addressof(sizes), ctypes.addressof(vals),
+            len(indexes[0].label_values), draws.data_ptr(), Pd, Ph, Pw, pad, pad_class, clamp_mode, image.data_ptr(),
+            None if label_map is None else label_map.data_ptr(), origins.data_ptr(), picked.data_ptr())
+    return args, (image, label_map, origins, picked), device, B, (items, ptrs, sizes, vals)
+
+
+def sample_patches(samples, indexes, draws, patch_size=(128, 128, 128), padding_mode="zeros", pad_class=0, clamp="both", out=None,
+                   affine=None, displacement=None, field_interpolation="linear"):
+    """indexes: index_scans' result for these samples.  Each index is checked against its sample by shape, dtypes and device;
+    label values, normalisation and percentiles, which a sample does not carry, are checked for agreement across the batch's
+    indexes (ValueError either way);
+    draws: float32 CUDA [B, 6], read on the device.  out: optional preallocated (image, label_map | None, origins, picked).
+    affine / displacement / field_interpolation: with a map or a field the patch is cut through it, rotate / zoom / elastic
+    deformation of the patch in the crop pass itself (patch_warp.sample_warped_patches, which this call then is); with both None
+    the launches are the plain crop's.
+    -> (image fp16 [B, 2, Pd, Ph, Pw], label_map uint8 [B, Pd, Ph, Pw] | None, origins int32 [B, 3], picked int32 [B, 4])."""
+    if affine is not None or displacement is not None:
+        from . import patch_warp
+        return patch_warp.sample_warped_patches(samples, indexes, draws, patch_size=patch_size, affine=affine,
+                                                displacement=displacement, field_interpolation=field_interpolation,
+                                                padding_mode=padding_mode, pad_class=pad_class, clamp=clamp, out=out)
+    args, outputs, device, _, keep = _prepare(samples, indexes, draws, patch_size, padding_mode, pad_class, clamp, out)
+    _lib.call_on(device, "micf_patch_sample", *args)
+    del keep
+    return outputs
 
 
 def sample_batch(samples, draws, patch_size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, normalisation="minmax",
-                 percentiles=(1, 99), padding_mode="zeros", pad_class=0, clamp="both", out=None):
+                 percentiles=(1, 99), padding_mode="zeros", pad_class=0, clamp="both", out=None, affine=None, displacement=None,
+                 field_interpolation="linear"):
     """index_scans + sample_patches in one call: the same results bit for bit (for scans that do not stay resident)."""
     samples = list(samples)
     indexes = index_scans(samples, label_values=label_values, normalisation=normalisation, percentiles=percentiles)
     return sample_patches(samples, indexes, draws, patch_size=patch_size, padding_mode=padding_mode, pad_class=pad_class,
-                          clamp=clamp, out=out)
+                          clamp=clamp, out=out, affine=affine, displacement=displacement, field_interpolation=field_interpolation)
 
 
 __all__ = ["index_scans", "draw_patches", "sample_patches", "sample_batch", "PatchIndex", "SEGMENT", "MMWHS_LABEL_VALUES",

@@ -16,6 +16,16 @@ scan B times, every sample forced onto a foreground voxel (the costly branch) wi
   crop_bytes           what the crop kernel must move per call: per output voxel two source elements, one label element, 4 bytes
                        of float16 and 1 byte of class
   ratio_aten / ratio_numpy = theirs / ours (above 1: the kernels are faster).
+
+    python tools/bench_patches.py --warp [--batches 1,2,8]                                      # the crop through a map / a field
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/bench_patches.py --warp --profile-only 8
+
+--warp times patches.sample_patches(..., affine=theta) and (..., affine=theta, displacement=field, field_interpolation="cubic") with
+affine.draw_affine / elastic.draw_elastic's default draws on the patch grid (a (7, 7, 7) field), per call with a preallocated `out`:
+  sample_ms            the plain sample_patches of the same session
+  warp_map_ms / warp_map_field_ms      the call through a map / through a map and the field
+  aten_map_ms / aten_map_field_ms      the ATen composition on the same GPU (aten_warp below), handed the origins
+  ratio_aten_* = theirs / ours; ratio_plain_map = warp_map_ms / sample_ms.
 """
 import argparse
 import json
@@ -125,6 +135,86 @@ def numpy_sample(host, stats, counts, draws_host, values, patch):
     return out
 
 
+def aten_warp(scan, stats, origins_host, theta, field, values, patch):
+    """What a user composes from ATen for a warped patch: per sample a crop of a window enlarged by half a patch on every side
+    (zero-padded where it leaves the scan), normalised in float32, and F.grid_sample of that window and of the one-hot label at
+    F.affine_grid's coordinates (plus the field, resized trilinearly: ATen has no cubic B-spline), argmax for the class."""
+    ct, mr, lab = scan
+    images, labels = [], []
+    K = len(values)
+    for b, o in enumerate(origins_host):
+        m = [p // 2 for p in patch]
+        sl, pad = [], []
+        for ax in range(3):
+            lo_w, hi_w = o[ax] - m[ax], o[ax] + patch[ax] + m[ax]
+            lo, hi = max(lo_w, 0), min(hi_w, lab.shape[ax])
+            sl.append(slice(lo, hi))
+            pad = [lo - lo_w, hi_w - hi] + pad
+        window = torch.stack([F.pad((vol[tuple(sl)].float() - mn) / (mx - mn), pad) for vol, (mn, mx) in zip((ct, mr), stats)])
+        raw = F.pad(lab[tuple(sl)], pad)
+        cls = torch.full(raw.shape, K + 1, dtype=torch.int64, device=raw.device)
+        cls[raw == 0] = 0
+        for k, val in enumerate(values):
+            cls[raw == val] = k + 1
+        onehot = F.one_hot(cls, K + 2).permute(3, 0, 1, 2).float()
+        n = F.affine_grid(torch.eye(3, 4, device=ct.device)[None], (1, 1) + tuple(patch), align_corners=False)
+        if field is not None:
+            n = n + F.interpolate(field[b:b + 1], size=patch, mode="trilinear", align_corners=True).permute(0, 2, 3, 4, 1)
+        grid = n @ theta[b, :, :3].T + theta[b, :, 3]
+        grid = grid * torch.tensor([patch[2] / window.shape[3], patch[1] / window.shape[2], patch[0] / window.shape[1]], device=ct.device)
+        images.append(F.grid_sample(window[None], grid, mode="bilinear", padding_mode="zeros", align_corners=False)[0].half())
+        labels.append(F.grid_sample(onehot[None], grid, mode="bilinear", padding_mode="zeros", align_corners=False)[0].argmax(0).to(torch.uint8))
+    return torch.stack(images), torch.stack(labels)
+
+
+def bench_warp(a, scan, index, shape, patch, values):
+    """--warp: sample_patches through a map, and through a map and a (7, 7, 7) cubic field, next to the plain sample_patches of the
+    same session and to aten_warp; one JSON line per batch size.  The image is compared with the ATen composition's where no tap
+    leaves the enlarged window (share of elements within 2 fp16 steps), the label as the share of equal voxels."""
+    from micformer_amd import affine, elastic, patches
+    V = patch[0] * patch[1] * patch[2]
+    stats = index[0].stats.cpu().tolist()
+    if a.profile_only:
+        B = a.profile_only
+        g = torch.Generator().manual_seed(1)
+        draws = patches.draw_patches(B, oversample_foreground_percent=1.0, generator=g, device="cuda")
+        theta = affine.draw_affine(B, size=patch, generator=g, device="cuda")
+        field = elastic.draw_elastic(B, size=patch, generator=g, device="cuda")
+        for _ in range(20):
+            patches.sample_patches([scan] * B, index * B, draws, patch_size=patch, affine=theta)
+        for _ in range(20):
+            patches.sample_patches([scan] * B, index * B, draws, patch_size=patch, affine=theta, displacement=field,
+                                   field_interpolation="cubic")
+        torch.cuda.synchronize()
+        print(json.dumps({"profile_only": True, "warp": True, "B": B, "calls": "20 with a map, then 20 with a map and a cubic field"}))
+        return
+    for B in [int(b) for b in a.batches.split(",")]:
+        g = torch.Generator().manual_seed(B)
+        draws = patches.draw_patches(B, oversample_foreground_percent=1.0, generator=g, device="cuda")
+        theta = affine.draw_affine(B, size=patch, generator=g, device="cuda")
+        field = elastic.draw_elastic(B, size=patch, generator=g, device="cuda")
+        samples, idx = [scan] * B, index * B
+        out = patches.sample_patches(samples, idx, draws, patch_size=patch)
+        plain = timed(lambda: patches.sample_patches(samples, idx, draws, patch_size=patch, out=out), a.min_seconds)
+        ours_map = timed(lambda: patches.sample_patches(samples, idx, draws, patch_size=patch, out=out, affine=theta), a.min_seconds)
+        kw = dict(affine=theta, displacement=field, field_interpolation="cubic")
+        ours_field = timed(lambda: patches.sample_patches(samples, idx, draws, patch_size=patch, out=out, **kw), a.min_seconds)
+        got = [t.clone() for t in patches.sample_patches(samples, idx, draws, patch_size=patch, affine=theta)]
+        origins_host = got[2].cpu().tolist()
+        aten_map = timed(lambda: aten_warp(scan, stats, origins_host, theta, None, values, patch), a.min_seconds)
+        aten_field = timed(lambda: aten_warp(scan, stats, origins_host, theta, field, values, patch), a.min_seconds)
+        ref_image, ref_label = aten_warp(scan, stats, origins_host, theta, None, values, patch)
+        close = (got[0].float() - ref_image.float()).abs() <= 2.0 ** -9 * ref_image.float().abs().clamp(min=2.0 ** -5)
+        row = {"case": f"{B} x warped patch {a.patch}^3 of " + "x".join(map(str, shape)) + " int16 pair + label", "B": B,
+               "sample_ms": round(plain, 4), "warp_map_ms": round(ours_map, 4), "warp_map_field_ms": round(ours_field, 4),
+               "aten_map_ms": round(aten_map, 4), "aten_map_field_ms": round(aten_field, 4),
+               "ratio_aten_map": round(aten_map / ours_map, 2), "ratio_aten_map_field": round(aten_field / ours_field, 2),
+               "ratio_plain_map": round(ours_map / plain, 2), "voxels": B * V,
+               "image_close_aten": round(float(close.float().mean()), 5),
+               "label_equal_aten": round(float((got[1] == ref_label).float().mean()), 5)}
+        print(json.dumps(row), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="1,2,8")
@@ -133,6 +223,9 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.5)
     ap.add_argument("--profile-only", type=int, default=0, metavar="B",
                     help="20 sample_patches calls of batch B and nothing else (for rocprofv3)")
+    ap.add_argument("--warp", action="store_true",
+                    help="time the crop through a map, and through a map and a (7, 7, 7) cubic field, next to the plain crop and an "
+                         "ATen composition (a crop of an enlarged window + F.grid_sample on image and one-hot label)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_patches.py needs the GPU")
@@ -142,6 +235,8 @@ def main():
     values = patches.MMWHS_LABEL_VALUES
     scan = make_scan(shape, values, 7)
     index = patches.index_scans([scan])
+    if a.warp:
+        return bench_warp(a, scan, index, shape, patch, values)
     V = patch[0] * patch[1] * patch[2]
     crop_bytes_per_sample = V * (2 * 2 + 2 + 4 + 1)
     if a.profile_only:
