@@ -8,6 +8,7 @@
 // otherwise (same arithmetic, same bits).  The separable weight of a voxel is rebuilt from three taps held in registers and is
 // worked out once per voxel (with the wsum update), not once per class.
 #include "common.h"
+#include "sw_rows.h"
 #include "../../include/micformer_blend.h"
 
 namespace {
@@ -16,23 +17,9 @@ constexpr int kBlendMax = 64;          // windows per call (kSwMax of misc.hip)
 constexpr int kBlendThreads = 256;
 constexpr int kBlendBlocks = 2048;     // grid cap; the rest is grid-strided (128^3 in 16-byte pieces is exactly 2048 x 256 items)
 
-// the ONE accumulate expression of this file: a single rounding, independent of the compiler's contraction setting
-__device__ __forceinline__ float blend_term(float acc, float w, float p) { return __builtin_fmaf(w, p, acc); }
-
-template <int VEC> struct Row;
-template <> struct Row<1> {
-  float v[1];
-  __device__ __forceinline__ void load(const float* p) { v[0] = *p; }
-  __device__ __forceinline__ void store(float* p) const { *p = v[0]; }
-};
-template <> struct Row<4> {
-  float v[4];
-  __device__ __forceinline__ void load(const float* p) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  }
-  __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
+using micf_sw::Row;          // a row piece of VEC floats, and blend_term(): the ONE accumulate expression (sw_rows.h)
+using micf_sw::aligned16;
+using micf_sw::blend_term;
 
 // pred: this window's [K, rd, rh, rw]; out / wsum: the window's sample, [K, D, H, W] / [D, H, W]; plane = D * H * W.
 // One item = VEC consecutive x of one (z, y) row, all K classes; items = rd * rh * (rw / VEC) < 2^31.
@@ -71,8 +58,6 @@ __global__ void __launch_bounds__(kBlendThreads) sw_blend_window_kernel(const fl
     }
   }
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

@@ -14,6 +14,12 @@ sw_batch_size.  The map is
 this library's definition (blend.py); parity with MONAI's compute_importance_map is UNPINNED as well, the referee is
 tests/sw_blend_ref.py.
 
+mirror_axes=(0, 1, 2) (nnU-Net's test-time mirroring, mirror.py) predicts every window under each flip of the chosen axes and
+averages the predictions flipped back: out[b, k, v] = sum_i sum_f w_i(v) p_{i,f}[k, M_f(v - o_i)] / sum_i sum_f w_i(v), the terms in
+(window, flip code) order.  Both flips are index arithmetic inside the crop and the accumulate (csrc/sw_mirror.hip), so it adds no
+pass and no buffer; in either mode it takes the generic path with the store-and-sum accumulate, and is bit-identical for the same
+predictions from run to run and for every sw_batch_size.  The referee is tests/sw_mirror_ref.py.
+
 The full-volume fp32 accumulator (8 x 512 x 512 x 256 = 2.1 GB for BASELINE config 5) and the visit counts stay in HBM; window
 crops, the accumulate and the final divide are HIP kernels (csrc/misc.hip); the predictor sees `sw_batch_size` windows per
 call -- the network is batch-independent, so any sw_batch_size gives the same result and large ones fill the GPU better.
@@ -22,7 +28,7 @@ import math
 
 import torch
 
-from . import _lib, blend
+from . import _lib, blend, mirror
 from ._lib import call, f32
 from .blend import importance_map  # noqa: F401  (public: the map sliding_window_inference applies)
 
@@ -130,7 +136,7 @@ class GraphedPredictor:
 
 
 def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.5, mode="constant", sigma_scale=0.125, *,
-                             graph=False, autocast=False):
+                             graph=False, autocast=False, mirror_axes=()):
     """inputs (B, C, D, H, W) on the GPU -> (B, K, D, H, W) fp32, K = the predictor's output channels.
     mode "constant" (MONAI's default: every voxel of a window weighs 1) or "gaussian" (blend.importance_map: sigma_scale, a positive
     float or one per axis, times the roi size is the Gaussian's sigma; ignored for "constant").  The Gaussian mode calls
@@ -138,10 +144,15 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     run to run and for every sw_batch_size; parity of its map with MONAI's is UNPINNED (blend.py states the definition).
     graph=True wraps the predictor in a GraphedPredictor (pass your own instance as `predictor` to reuse it across volumes).
     autocast=True runs the predictor with bf16 matrix-core operands -- this library's counterpart of the
-    `torch.cuda.amp.autocast()` the reference wraps the call in (utils.py:236-238; fp16 there)."""
+    `torch.cuda.amp.autocast()` the reference wraps the call in (utils.py:236-238; fp16 there).
+    mirror_axes: a subset of (0, 1, 2) = (D, H, W); every window is predicted under each of the 2^k flips of these axes and the
+    predictions, flipped back, are averaged (mirror.py).  In either mode this calls `predictor(win)` on `sw_batch_size` (window,
+    flip) pairs at a time and is bit-identical for every sw_batch_size; () is the call without mirroring, launch for launch."""
     if graph and not isinstance(predictor, GraphedPredictor):
         predictor = GraphedPredictor(predictor)
     gaussian = blend.check_mode(mode) == "gaussian"
+    codes = mirror.flip_codes(mirror_axes)
+    mirrored = len(codes) > 1
     if gaussian:
         blend.sigma_scales(sigma_scale)
     if inputs.dim() != 5 or not inputs.is_cuda:
@@ -158,6 +169,8 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     V = Dp * Hp * Wp
     slices = [(b, z, y, xx) for z in sliding_window_starts(Dp, rd, overlap) for y in sliding_window_starts(Hp, rh, overlap)
               for xx in sliding_window_starts(Wp, rw, overlap) for b in range(B)]
+    if mirrored:       # items (b, z0, y0, x0, flip), window-major: a voxel's terms arrive in (window, flip code) order for every sw
+        slices = [s + (f,) for s in slices for f in codes]
     sw = min(max(int(sw_batch_size), 1), 64)
     out = count = None
     from . import ops
@@ -165,10 +178,9 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     # adds its logits straight into the volume accumulator at the window origins and bumps the visit counts in its last launch --
     # no [n, K, roi] prediction tensor, no accumulate launch.  Needs roi dims that the patch size divides (else the model pads).
     base = predictor.predictor if isinstance(predictor, GraphedPredictor) else predictor
-    fused = not gaussian and FUSE_ACCUMULATE and hasattr(base, "forward_accumulate") and hasattr(base, "out_conv") \
+    fused = not gaussian and not mirrored and FUSE_ACCUMULATE and hasattr(base, "forward_accumulate") and hasattr(base, "out_conv") \
         and getattr(base, "can_accumulate", lambda roi: False)((rd, rh, rw))      # (else: the generic crop / predict / accumulate path)
-    if gaussian:
-        taps, floor = blend.device_taps((rd, rh, rw), sigma_scale, x.device)
+    taps, floor = blend.device_taps((rd, rh, rw), sigma_scale, x.device) if gaussian else (None, 1.0)
     with torch.no_grad():
         if fused:
             K = base.out_conv.out_channels
@@ -197,7 +209,8 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
             slices = []
         for i in range(0, len(slices), sw):
             chunk = slices[i:i + sw]
-            win = ops.sw_window_batch(x, chunk, (rd, rh, rw))                 # ONE launch crops the whole batch of windows
+            # ONE launch crops the whole batch of windows (mirrored: each under its item's flip)
+            win = mirror.window_batch(x, chunk, (rd, rh, rw)) if mirrored else ops.sw_window_batch(x, chunk, (rd, rh, rw))
             if autocast:
                 prev = ops.arith_mode()
                 ops.set_compute_dtype("bf16")
@@ -213,7 +226,9 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
                 K = pred.shape[1]
                 out = ops.zero_(torch.empty((B, K, Dp, Hp, Wp), dtype=torch.float32, device=x.device))
                 count = ops.zero_(torch.empty((B, Dp, Hp, Wp), dtype=torch.float32, device=x.device))
-            if gaussian:
+            if mirrored:
+                mirror.accumulate(pred, out, count, chunk, taps, floor)      # one launch per item, in order, flipped back
+            elif gaussian:
                 blend.accumulate(pred, out, count, chunk, taps, floor)       # one launch per window, in order: `count` is sum(w)
             else:
                 ops.sw_accumulate_batch(pred, out, count, chunk)              # ONE launch adds it into the volume accumulator

@@ -126,16 +126,23 @@ def restore_labels(logits, shape, label_values=MMWHS_LABEL_VALUES, probabilities
 
 
 def segment_pair(model, ct, mr, size=(128, 128, 128), label_values=MMWHS_LABEL_VALUES, probabilities=False, keep_largest=False,
-                 normalisation="minmax", percentiles=(1, 99)):
+                 normalisation="minmax", percentiles=(1, 99), mirror_axes=()):
     """Raw CT / MR volumes of one sample (own-shaped (d, h, w) CUDA tensors, int16 / float32) -> the label volume of the CT's own
     shape: loader.load_pair -> data.prepare_raw_batch(image, None, None) (the validation transform) -> model under no_grad ->
     restore_labels at ct.shape.  keep_largest=True: the restored volume then goes through postprocess.keep_largest_components in
-    place (of every class only its largest 26-connected component stays).  normalisation / percentiles: loader.load_pair's."""
-    from . import data, loader
+    place (of every class only its largest 26-connected component stays).  normalisation / percentiles: loader.load_pair's.
+    mirror_axes: a subset of (0, 1, 2) = (D, H, W) for test-time mirroring; the logits are then mirror.mirrored_logits, the model's
+    logits under each flip of these axes, flipped back and averaged (the input of a flip is a mirrored copy of the loaded image,
+    bit for bit, and the validation transform runs on it inside the model as it does on the unflipped one)."""
+    from . import data, loader, mirror
+    mirrored = len(mirror.flip_codes(mirror_axes)) > 1
     image, _, _ = loader.load_pair(ct, mr, None, size=size, normalisation=normalisation, percentiles=percentiles)
     x, _ = data.prepare_raw_batch(image.unsqueeze(0), None, None)
-    with torch.no_grad():
-        logits = model(x)
+    if mirrored:
+        logits = mirror.mirrored_logits(model, x, mirror_axes)
+    else:
+        with torch.no_grad():
+            logits = model(x)
     labels = restore_labels(logits.float().contiguous(), tuple(ct.shape), label_values=label_values, probabilities=probabilities)
     if keep_largest:
         from . import postprocess
