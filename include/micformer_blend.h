@@ -1,7 +1,7 @@
 /*
  * micformer_blend.h -- C-ABI of the weighted accumulate of sliding-window inference with mode="gaussian" (the counterpart of
  * monai.inferers.sliding_window_inference(mode="gaussian"); micformer_amd/inference.py, micformer_amd/blend.py).  Conventions are
- * those of micformer_hip.h.  Kernel: micformer_amd/csrc/sw_blend.hip; rules: DESIGN.md "Sliding-window inference".
+ * those of micformer_hip.h.  Kernel: micformer_amd/csrc/sliding_window.hip; rules: DESIGN.md "Sliding-window inference".
  *
  * The importance map of a window of (rd, rh, rw) voxels is separable.  The HOST builds three tap vectors g0 | g1 | g2 (float32,
  * g_i[j] = exp(-(j - (n_i - 1) / 2)^2 / (2 sigma_i^2)), sigma_i = sigma_scale_i * n_i) and floor = max(min of their outer product,

@@ -327,7 +327,10 @@ int micf_conv_up_bwd_weight(const float* dy, const float* x, float* dw, float* d
  * predictor, overlap), mode="constant"), one batch element, NCDHW fp32:
  *   window:     win[c, z, y, x] = vol[c, z0+z, y0+y, x0+x]                  (the predictor's input crop)
  *   accumulate: out[k, z0+z, y0+y, x0+x] += pred[k, z, y, x];  count[z0+z, y0+y, x0+x] += 1
- *   normalize:  out[k, v] /= count[v]                                       (every voxel is covered at least once) */
+ *   normalize:  out[k, v] /= count[v]                                       (every voxel is covered at least once)
+ * Kernels: micformer_amd/csrc/sliding_window.hip, shared with micformer_blend.h and micformer_mirror.h.  For window, accumulate
+ * and their batched forms: MICF_EINVAL for a NULL pointer, a non-positive extent or a window that leaves the volume (checked in
+ * 64 bits: an origin near INT32_MAX is an error, not an overflow); MICF_EUNSUPPORTED for a window of rd * rh * rw >= 2^31 voxels. */
 int micf_sw_window(const float* vol, float* win, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0, int x0,
                    micf_stream_t stream);
 int micf_sw_accumulate(const float* pred, float* out, float* count, int K, int D, int H, int W, int rd, int rh, int rw, int z0,
@@ -335,7 +338,8 @@ int micf_sw_accumulate(const float* pred, float* out, float* count, int K, int D
 int micf_sw_normalize(float* out, const float* count, int K, int64_t V, micf_stream_t stream);
 /* Batched forms: crop `n` <= 64 windows of vol [B,C,D,H,W] into win [n,C,rd,rh,rw] / accumulate `n`
  * predictions [n,K,rd,rh,rw] into out [B,K,D,H,W] and count [B,D,H,W] in ONE launch each.  coords: HOST int32 [n,4] = (b, z0, y0,
- * x0), read during the call.  Windows of a batch may overlap (fp32 atomic adds). */
+ * x0), read during the call; n outside 1..64 or b outside 0..B-1 is MICF_EINVAL.  Windows of a batch may overlap (fp32 atomic
+ * adds). */
 int micf_sw_window_batch(const float* vol, float* win, const int32_t* coords, int n, int B, int C, int D, int H, int W, int rd,
                          int rh, int rw, micf_stream_t stream);
 int micf_sw_accumulate_batch(const float* pred, float* out, float* count, const int32_t* coords, int n, int B, int K, int D, int H,

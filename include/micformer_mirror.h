@@ -1,7 +1,7 @@
 /*
  * micformer_mirror.h -- C-ABI of test-time mirroring for sliding-window inference (nnU-Net's default at prediction time;
  * micformer_amd/inference.py mirror_axes=, micformer_amd/mirror.py).  Conventions and error codes are those of micformer_blend.h /
- * micformer_hip.h.  Kernels: micformer_amd/csrc/sw_mirror.hip; rules: DESIGN.md "Sliding-window inference".
+ * micformer_hip.h.  Kernels: micformer_amd/csrc/sliding_window.hip; rules: DESIGN.md "Sliding-window inference".
  *
  * A flip code f is a 3-bit mask: bit 0 reverses D, bit 1 H, bit 2 W.  M_f maps a window index (z, y, x) of a (rd, rh, rw) window to
  * (f&1 ? rd-1-z : z, f&2 ? rh-1-y : y, f&4 ? rw-1-x : x); it is its own inverse.  An item is (b, z0, y0, x0, f): a window origin and

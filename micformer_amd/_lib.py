@@ -424,6 +424,14 @@ def profile_stop():
     return out
 
 
+def int32_rows(rows, width):
+    """A list of `width`-tuples of ints -> the HOST int32 array [n, width] that an entry point reads during the call (window
+    coordinates); pass it as the pointer argument."""
+    if any(len(r) != width for r in rows):
+        raise ValueError(f"expected rows of {width} ints, got {list(rows)!r}")
+    return (ctypes.c_int32 * (width * len(rows)))(*[v for r in rows for v in r])
+
+
 def f32(t):
     if t is None:
         return None

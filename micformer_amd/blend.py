@@ -1,5 +1,5 @@
-"""Importance maps and the weighted accumulate of sliding-window inference: the binding of include/micformer_blend.h (kernel:
-csrc/sw_blend.hip) and the host side of `inference.sliding_window_inference(mode="gaussian")`.
+"""Importance maps and the weighted accumulate of sliding-window inference: the binding of include/micformer_blend.h (kernels:
+csrc/sliding_window.hip) and the host side of `inference.sliding_window_inference(mode="gaussian")`.
 
     w = blend.importance_map((128, 128, 128), "gaussian", sigma_scale=0.125)        # float32 [rd, rh, rw]
 
@@ -11,7 +11,6 @@ Per axis i of n_i voxels, sigma_i = sigma_scale_i * n_i and, in float32 on the h
 The host builds the three tap vectors and `floor`; the device rebuilds max((g0[z] * g1[y]) * g2[x], floor) with the same two float32
 multiplies, so its weights are bit-equal to `importance_map()`.
 """
-import ctypes
 import math
 
 import torch
@@ -91,19 +90,40 @@ def device_taps(roi_size, sigma_scale, device):
     return torch.cat(taps).to(device).contiguous(), floor
 
 
+def store_and_sum(entry, width, pred, out, wsum, items, taps, floor):
+    """The store-and-sum accumulate behind accumulate() and mirror.accumulate(): C entry point `entry`, whose items have `width`
+    ints; taps None: no taps."""
+    B, K, D, H, W = out.shape
+    rd, rh, rw = pred.shape[2:]
+    if pred.shape[0] != len(items) or pred.shape[1] != K or tuple(wsum.shape) != (B, D, H, W) or \
+            (taps is not None and taps.numel() != rd + rh + rw):
+        raise ValueError(f"{entry}: pred {tuple(pred.shape)}, out {tuple(out.shape)}, wsum {tuple(wsum.shape)}, {len(items)} items "
+                         f"and {'no' if taps is None else taps.numel()} taps do not fit together")
+    _lib.call(entry, _lib.f32(pred), _lib.f32(out), _lib.f32(wsum), _lib.int32_rows(items, width), len(items), B, K, D, H, W,
+              rd, rh, rw, _lib.f32(taps), floor)
+
+
 def accumulate(pred, out, wsum, chunk, taps, floor):
     """pred [n, K, rd, rh, rw] weighted into out [B, K, D, H, W] and wsum [B, D, H, W] at the windows of `chunk` (a list of
     (b, z0, y0, x0)): one launch per window in list order, no atomics (include/micformer_blend.h)."""
-    B, K, D, H, W = out.shape
-    rd, rh, rw = pred.shape[2:]
-    if pred.shape[0] != len(chunk) or pred.shape[1] != K or tuple(wsum.shape) != (B, D, H, W) or taps.numel() != rd + rh + rw:
-        raise ValueError(f"blend.accumulate: pred {tuple(pred.shape)}, out {tuple(out.shape)}, wsum {tuple(wsum.shape)}, "
-                         f"{len(chunk)} windows and {taps.numel()} taps do not fit together")
-    arr = (ctypes.c_int32 * (4 * len(chunk)))()
-    for i, (b, z, y, x) in enumerate(chunk):
-        arr[4 * i:4 * i + 4] = [b, z, y, x]
-    _lib.call("micf_sw_blend_accumulate", _lib.f32(pred), _lib.f32(out), _lib.f32(wsum), ctypes.cast(arr, ctypes.c_void_p),
-              len(chunk), B, K, D, H, W, rd, rh, rw, _lib.f32(taps), floor)
+    store_and_sum("micf_sw_blend_accumulate", 4, pred, out, wsum, chunk, taps, floor)
 
 
-__all__ = ["MODES", "SIGNATURES", "accumulate", "check_mode", "device_taps", "gaussian_taps", "importance_map", "sigma_scales"]
+def new_sums(B, K, D, H, W, device, reuse=None):
+    """-> (out [B, K, D, H, W], wsum [B, D, H, W]): the float32 sums of a volume, zeroed (one memset node each); `reuse`: a pair
+    of these shapes to zero and return instead of a new one."""
+    out, wsum = reuse or (torch.empty((B, K, D, H, W), dtype=torch.float32, device=device),
+                          torch.empty((B, D, H, W), dtype=torch.float32, device=device))
+    for t in (out, wsum):
+        _lib.call("micf_zero", _lib.ptr(t), t.numel() * 4)
+    return out, wsum
+
+
+def normalize(out, wsum):
+    """out[b, k, v] /= wsum[b, v] in place: micf_sw_normalize, one launch per sample."""
+    for o, w in zip(out, wsum):
+        _lib.call("micf_sw_normalize", _lib.f32(o), _lib.f32(w), o.shape[0], w.numel())
+
+
+__all__ = ["MODES", "SIGNATURES", "accumulate", "check_mode", "device_taps", "gaussian_taps", "importance_map", "new_sums",
+           "normalize", "sigma_scales", "store_and_sum"]

@@ -56,36 +56,6 @@ __global__ void __launch_bounds__(256) resize_kernel(const float* __restrict__ a
   }
 }
 
-
-// ---- sliding-window inference (utils.py:226-234: monai sliding_window_inference, mode="constant"): accumulate one window's
-// logits into the full-volume fp32 sum and bump the per-voxel visit count; then out = sum / count.
-__global__ void __launch_bounds__(256) sw_window_kernel(const float* __restrict__ vol, float* __restrict__ win, int C, int D, int H,
-                                                        int W, int rd, int rh, int rw, int z0, int y0, int x0, int64_t total) {
-  // win[c, z, y, x] = vol[c, z0+z, y0+y, x0+x]   (one batch element; NCDHW)
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int x = (int)(i % rw); int64_t r = i / rw;
-    const int y = (int)(r % rh); r /= rh;
-    const int z = (int)(r % rd); const int c = (int)(r / rd);
-    win[i] = vol[(((int64_t)c * D + z0 + z) * H + y0 + y) * W + x0 + x];
-  }
-}
-__global__ void __launch_bounds__(256) sw_accumulate_kernel(const float* __restrict__ pred, float* __restrict__ out,
-                                                            float* __restrict__ count, int K, int D, int H, int W, int rd, int rh,
-                                                            int rw, int z0, int y0, int x0, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int x = (int)(i % rw); int64_t r = i / rw;
-    const int y = (int)(r % rh); r /= rh;
-    const int z = (int)(r % rd); const int k = (int)(r / rd);
-    const int64_t v = ((int64_t)(z0 + z) * H + y0 + y) * W + x0 + x;
-    out[(int64_t)k * D * H * W + v] += pred[i];
-    if (k == 0) count[v] += 1.f;
-  }
-}
-__global__ void __launch_bounds__(256) sw_normalize_kernel(float* __restrict__ out, const float* __restrict__ count, int64_t V,
-                                                           int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) out[i] /= count[i % V];
-}
-
 }  // namespace micf
 using namespace micf;
 
@@ -163,33 +133,6 @@ extern "C" int micf_resize_trilinear_bwd(const float* ddst, float* dsrc, int B, 
   if (hipMemsetAsync(dsrc, 0, sizeof(float) * (size_t)B * D * H * W * C, s) != hipSuccess) return MICF_ELAUNCH;
   const int64_t total = (int64_t)B * Do * Ho * Wo * C;
   hipLaunchKernelGGL(resize_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, ddst, dsrc, B, D, H, W, Do, Ho, Wo, C, total);
-  MICF_RETURN_LAUNCH();
-}
-
-extern "C" int micf_sw_window(const float* vol, float* win, int C, int D, int H, int W, int rd, int rh, int rw, int z0, int y0,
-                              int x0, micf_stream_t stream) {
-  if (!vol || !win || C <= 0 || rd <= 0 || rh <= 0 || rw <= 0 || z0 < 0 || y0 < 0 || x0 < 0 || z0 + rd > D || y0 + rh > H ||
-      x0 + rw > W)
-    return MICF_EINVAL;
-  const int64_t total = (int64_t)C * rd * rh * rw;
-  hipLaunchKernelGGL(sw_window_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, vol, win, C, D, H, W, rd, rh, rw, z0,
-                     y0, x0, total);
-  MICF_RETURN_LAUNCH();
-}
-extern "C" int micf_sw_accumulate(const float* pred, float* out, float* count, int K, int D, int H, int W, int rd, int rh, int rw,
-                                  int z0, int y0, int x0, micf_stream_t stream) {
-  if (!pred || !out || !count || K <= 0 || rd <= 0 || rh <= 0 || rw <= 0 || z0 < 0 || y0 < 0 || x0 < 0 || z0 + rd > D ||
-      y0 + rh > H || x0 + rw > W)
-    return MICF_EINVAL;
-  const int64_t total = (int64_t)K * rd * rh * rw;
-  hipLaunchKernelGGL(sw_accumulate_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, pred, out, count, K, D, H, W, rd,
-                     rh, rw, z0, y0, x0, total);
-  MICF_RETURN_LAUNCH();
-}
-extern "C" int micf_sw_normalize(float* out, const float* count, int K, int64_t V, micf_stream_t stream) {
-  if (!out || !count || K <= 0 || V <= 0) return MICF_EINVAL;
-  const int64_t total = (int64_t)K * V;
-  hipLaunchKernelGGL(sw_normalize_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, out, count, V, total);
   MICF_RETURN_LAUNCH();
 }
 
@@ -327,70 +270,6 @@ extern "C" int micf_weight_prep_grouped(const micf_weight_prep_item* items, int 
     if (hipGetLastError() != hipSuccess) return MICF_ELAUNCH;
   }
   return MICF_OK;
-}
-
-// ---- sliding-window inference, batched: one launch crops `n` windows, one launch accumulates `n` predictions (windows of a
-// batch may overlap: fp32 atomics; the sum over <= 8 visits is order-independent to an ulp)
-namespace micf {
-constexpr int kSwMax = 64;
-struct SwCoords { int n; int b[kSwMax], z[kSwMax], y[kSwMax], x[kSwMax]; };
-__global__ void __launch_bounds__(256) sw_window_batch_kernel(const float* __restrict__ vol, float* __restrict__ win, SwCoords c, int C,
-                                                              int D, int H, int W, int rd, int rh, int rw, int64_t per) {
-  const int n = blockIdx.y;
-  const float* v = vol + (int64_t)c.b[n] * C * D * H * W;
-  float* o = win + (int64_t)n * per;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
-    const int x = (int)(i % rw); int64_t r = i / rw;
-    const int y = (int)(r % rh); r /= rh;
-    const int z = (int)(r % rd); const int ch = (int)(r / rd);
-    o[i] = v[(((int64_t)ch * D + c.z[n] + z) * H + c.y[n] + y) * W + c.x[n] + x];
-  }
-}
-__global__ void __launch_bounds__(256) sw_accumulate_batch_kernel(const float* __restrict__ pred, float* __restrict__ out,
-                                                                  float* __restrict__ count, SwCoords c, int K, int D, int H, int W,
-                                                                  int rd, int rh, int rw, int64_t per) {
-  const int n = blockIdx.y;
-  const float* p = pred + (int64_t)n * per;
-  float* o = out + (int64_t)c.b[n] * K * D * H * W;
-  float* cn = count + (int64_t)c.b[n] * D * H * W;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per; i += (int64_t)gridDim.x * 256) {
-    const int x = (int)(i % rw); int64_t r = i / rw;
-    const int y = (int)(r % rh); r /= rh;
-    const int z = (int)(r % rd); const int k = (int)(r / rd);
-    const int64_t v = ((int64_t)(c.z[n] + z) * H + c.y[n] + y) * W + c.x[n] + x;
-    atomicAdd(o + (int64_t)k * D * H * W + v, p[i]);
-    if (k == 0) atomicAdd(cn + v, 1.f);
-  }
-}
-static bool sw_coords(SwCoords& c, const int32_t* coords, int n, int B, int D, int H, int W, int rd, int rh, int rw) {
-  if (!coords || n <= 0 || n > kSwMax) return false;
-  c.n = n;
-  for (int i = 0; i < n; ++i) {
-    c.b[i] = coords[4 * i]; c.z[i] = coords[4 * i + 1]; c.y[i] = coords[4 * i + 2]; c.x[i] = coords[4 * i + 3];
-    if (c.b[i] < 0 || c.b[i] >= B || c.z[i] < 0 || c.y[i] < 0 || c.x[i] < 0 || c.z[i] + rd > D || c.y[i] + rh > H || c.x[i] + rw > W) return false;
-  }
-  return true;
-}
-}  // namespace micf
-
-extern "C" int micf_sw_window_batch(const float* vol, float* win, const int32_t* coords, int n, int B, int C, int D, int H, int W,
-                                    int rd, int rh, int rw, micf_stream_t stream) {
-  micf::SwCoords c;
-  if (!vol || !win || C <= 0 || rd <= 0 || rh <= 0 || rw <= 0 || !micf::sw_coords(c, coords, n, B, D, H, W, rd, rh, rw)) return MICF_EINVAL;
-  const int64_t per = (int64_t)C * rd * rh * rw;
-  hipLaunchKernelGGL(micf::sw_window_batch_kernel, dim3(grid_for(per) > 2048 ? 2048 : grid_for(per), n), dim3(256), 0, (hipStream_t)stream,
-                     vol, win, c, C, D, H, W, rd, rh, rw, per);
-  MICF_RETURN_LAUNCH();
-}
-extern "C" int micf_sw_accumulate_batch(const float* pred, float* out, float* count, const int32_t* coords, int n, int B, int K, int D,
-                                        int H, int W, int rd, int rh, int rw, micf_stream_t stream) {
-  micf::SwCoords c;
-  if (!pred || !out || !count || K <= 0 || rd <= 0 || rh <= 0 || rw <= 0 || !micf::sw_coords(c, coords, n, B, D, H, W, rd, rh, rw))
-    return MICF_EINVAL;
-  const int64_t per = (int64_t)K * rd * rh * rw;
-  hipLaunchKernelGGL(micf::sw_accumulate_batch_kernel, dim3(grid_for(per) > 2048 ? 2048 : grid_for(per), n), dim3(256), 0,
-                     (hipStream_t)stream, pred, out, count, c, K, D, H, W, rd, rh, rw, per);
-  MICF_RETURN_LAUNCH();
 }
 
 // ---- input-pipeline tail (train.py:116-125: RandFlipd x3 on image + label, NormalizeIntensityd(nonzero, channel_wise),

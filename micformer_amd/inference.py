@@ -9,27 +9,28 @@ The referee is oracle/micformer_ref.py::sliding_window_inference (parity with MO
 mode="gaussian" (nnU-Net's default blending) weights every window with the separable Gaussian importance map of blend.py:
 out[b, k, v] = sum_i w_i(v) p_i[k, v] / sum_i w_i(v) over the windows i that cover v, in the order they are enumerated here (z, y, x,
 then b).  It always takes the generic path -- predictor(win), then one plain read-modify-write launch per window
-(csrc/sw_blend.hip, no float atomics) -- so for the same predictions its result is bit-identical from run to run and for every
+(csrc/sliding_window.hip, no float atomics) -- so for the same predictions its result is bit-identical from run to run and for every
 sw_batch_size.  The map is
 this library's definition (blend.py); parity with MONAI's compute_importance_map is UNPINNED as well, the referee is
 tests/sw_blend_ref.py.
 
 mirror_axes=(0, 1, 2) (nnU-Net's test-time mirroring, mirror.py) predicts every window under each flip of the chosen axes and
 averages the predictions flipped back: out[b, k, v] = sum_i sum_f w_i(v) p_{i,f}[k, M_f(v - o_i)] / sum_i sum_f w_i(v), the terms in
-(window, flip code) order.  Both flips are index arithmetic inside the crop and the accumulate (csrc/sw_mirror.hip), so it adds no
+(window, flip code) order.  Both flips are index arithmetic inside the crop and the accumulate (csrc/sliding_window.hip), so it adds no
 pass and no buffer; in either mode it takes the generic path with the store-and-sum accumulate, and is bit-identical for the same
 predictions from run to run and for every sw_batch_size.  The referee is tests/sw_mirror_ref.py.
 
 The full-volume fp32 accumulator (8 x 512 x 512 x 256 = 2.1 GB for BASELINE config 5) and the visit counts stay in HBM; window
-crops, the accumulate and the final divide are HIP kernels (csrc/misc.hip); the predictor sees `sw_batch_size` windows per
+crops, the accumulate and the final divide are HIP kernels (csrc/sliding_window.hip); the predictor sees `sw_batch_size` windows per
 call -- the network is batch-independent, so any sw_batch_size gives the same result and large ones fill the GPU better.
 """
+import contextlib
+import functools
 import math
 
 import torch
 
-from . import _lib, blend, mirror
-from ._lib import call, f32
+from . import blend, mirror
 from .blend import importance_map  # noqa: F401  (public: the map sliding_window_inference applies)
 
 
@@ -135,6 +136,19 @@ class GraphedPredictor:
         graph.replay()
 
 
+@contextlib.contextmanager
+def _bf16_predictor(on):
+    """The predictor runs in bf16 mode inside (`on`; else in the mode that is set); the mode is restored after."""
+    from . import ops
+    prev = ops.arith_mode()
+    if on:
+        ops.set_compute_dtype("bf16")
+    try:
+        yield
+    finally:
+        ops.set_compute_dtype(prev)
+
+
 def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap=0.5, mode="constant", sigma_scale=0.125, *,
                              graph=False, autocast=False, mirror_axes=()):
     """inputs (B, C, D, H, W) on the GPU -> (B, K, D, H, W) fp32, K = the predictor's output channels.
@@ -159,14 +173,13 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
         raise ValueError("sliding_window_inference expects a (B, C, D, H, W) CUDA (ROCm) tensor")
     if isinstance(roi_size, int):
         roi_size = (roi_size,) * 3
-    rd, rh, rw = (int(r) for r in roi_size)
+    roi = rd, rh, rw = tuple(int(r) for r in roi_size)
     x = inputs.float().contiguous()
     B, C, D, H, W = x.shape
     pd, ph, pw = max(rd - D, 0), max(rh - H, 0), max(rw - W, 0)
     if pd or ph or pw:       # image smaller than the ROI: symmetric zero padding, cropped away again at the end
         x = torch.nn.functional.pad(x, (pw // 2, pw - pw // 2, ph // 2, ph - ph // 2, pd // 2, pd - pd // 2)).contiguous()
     Dp, Hp, Wp = x.shape[2:]
-    V = Dp * Hp * Wp
     slices = [(b, z, y, xx) for z in sliding_window_starts(Dp, rd, overlap) for y in sliding_window_starts(Hp, rh, overlap)
               for xx in sliding_window_starts(Wp, rw, overlap) for b in range(B)]
     if mirrored:       # items (b, z0, y0, x0, flip), window-major: a voxel's terms arrive in (window, flip code) order for every sw
@@ -179,61 +192,40 @@ def sliding_window_inference(inputs, roi_size, sw_batch_size, predictor, overlap
     # no [n, K, roi] prediction tensor, no accumulate launch.  Needs roi dims that the patch size divides (else the model pads).
     base = predictor.predictor if isinstance(predictor, GraphedPredictor) else predictor
     fused = not gaussian and not mirrored and FUSE_ACCUMULATE and hasattr(base, "forward_accumulate") and hasattr(base, "out_conv") \
-        and getattr(base, "can_accumulate", lambda roi: False)((rd, rh, rw))      # (else: the generic crop / predict / accumulate path)
-    taps, floor = blend.device_taps((rd, rh, rw), sigma_scale, x.device) if gaussian else (None, 1.0)
+        and getattr(base, "can_accumulate", lambda roi: False)(roi)      # (else: the generic crop / predict / accumulate path)
     with torch.no_grad():
         if fused:
             K = base.out_conv.out_channels
             cached = isinstance(predictor, GraphedPredictor)
-            if cached:
-                out, count = predictor.accumulators((B, K, Dp, Hp, Wp), x.device)
-            else:
-                out = torch.empty((B, K, Dp, Hp, Wp), dtype=torch.float32, device=x.device)
-                count = torch.empty((B, Dp, Hp, Wp), dtype=torch.float32, device=x.device)
-            ops.zero_(out)
-            ops.zero_(count)
-            prev = ops.arith_mode()
-            if autocast:
-                ops.set_compute_dtype("bf16")
-            try:
+            out, count = blend.new_sums(B, K, Dp, Hp, Wp, x.device,
+                                        reuse=predictor.accumulators((B, K, Dp, Hp, Wp), x.device) if cached else None)
+            accumulate = predictor.accumulate if cached else base.forward_accumulate
+            with _bf16_predictor(autocast):
                 for i in range(0, len(slices), sw):
                     chunk = slices[i:i + sw]
-                    win = ops.sw_window_batch(x, chunk, (rd, rh, rw))
-                    coords = torch.tensor(chunk, dtype=torch.int32).to(x.device, non_blocking=True)
-                    if isinstance(predictor, GraphedPredictor):
-                        predictor.accumulate(win, out, count, coords)
-                    else:
-                        base.forward_accumulate(win, out, count, coords)
-            finally:
-                ops.set_compute_dtype(prev)
-            slices = []
-        for i in range(0, len(slices), sw):
-            chunk = slices[i:i + sw]
-            # ONE launch crops the whole batch of windows (mirrored: each under its item's flip)
-            win = mirror.window_batch(x, chunk, (rd, rh, rw)) if mirrored else ops.sw_window_batch(x, chunk, (rd, rh, rw))
-            if autocast:
-                prev = ops.arith_mode()
-                ops.set_compute_dtype("bf16")
-                try:
+                    win = ops.sw_window_batch(x, chunk, roi)
+                    accumulate(win, out, count, torch.tensor(chunk, dtype=torch.int32).to(x.device, non_blocking=True))
+        else:
+            # ONE launch crops the whole batch of windows (mirrored: each under its item's flip); then one accumulate launch per
+            # item in order, flipped back (mirrored), one per window in order with `count` = sum(w) (Gaussian), or ONE that adds
+            # the batch into the volume accumulator with atomics
+            crop = mirror.window_batch if mirrored else ops.sw_window_batch
+            if mirrored or gaussian:
+                taps, floor = blend.device_taps(roi, sigma_scale, x.device) if gaussian else (None, 1.0)
+                accumulate = functools.partial(mirror.accumulate if mirrored else blend.accumulate, taps=taps, floor=floor)
+            else:
+                accumulate = ops.sw_accumulate_batch
+            for i in range(0, len(slices), sw):
+                chunk = slices[i:i + sw]
+                win = crop(x, chunk, roi)
+                with _bf16_predictor(autocast):
                     pred = predictor(win).float().contiguous()
-                finally:
-                    ops.set_compute_dtype(prev)
-            else:
-                pred = predictor(win).float().contiguous()
-            if pred.shape[0] != len(chunk) or tuple(pred.shape[2:]) != (rd, rh, rw):
-                raise ValueError(f"predictor returned {tuple(pred.shape)} for windows {tuple(win.shape)}")
-            if out is None:
-                K = pred.shape[1]
-                out = ops.zero_(torch.empty((B, K, Dp, Hp, Wp), dtype=torch.float32, device=x.device))
-                count = ops.zero_(torch.empty((B, Dp, Hp, Wp), dtype=torch.float32, device=x.device))
-            if mirrored:
-                mirror.accumulate(pred, out, count, chunk, taps, floor)      # one launch per item, in order, flipped back
-            elif gaussian:
-                blend.accumulate(pred, out, count, chunk, taps, floor)       # one launch per window, in order: `count` is sum(w)
-            else:
-                ops.sw_accumulate_batch(pred, out, count, chunk)              # ONE launch adds it into the volume accumulator
-        for b in range(B):
-            call("micf_sw_normalize", f32(out[b]), f32(count[b]), K, V)
+                if pred.shape[0] != len(chunk) or tuple(pred.shape[2:]) != roi:
+                    raise ValueError(f"predictor returned {tuple(pred.shape)} for windows {tuple(win.shape)}")
+                if out is None:
+                    out, count = blend.new_sums(B, pred.shape[1], Dp, Hp, Wp, x.device)
+                accumulate(pred, out, count, chunk)
+        blend.normalize(out, count)
         if fused and cached:
             out = out.clone()                             # (the accumulator itself stays with the predictor's graphs)
     if pd or ph or pw:

@@ -1,5 +1,5 @@
 """Test-time mirroring (nnU-Net's default at prediction time): the binding of include/micformer_mirror.h (kernels:
-csrc/sw_mirror.hip) and the host side of `inference.sliding_window_inference(mirror_axes=...)` and
+csrc/sliding_window.hip) and the host side of `inference.sliding_window_inference(mirror_axes=...)` and
 `restore.segment_pair(mirror_axes=...)`.
 
     out = sliding_window_inference(x, 128, 7, model, mode="gaussian", mirror_axes=(0, 1, 2))
@@ -11,11 +11,9 @@ An item is (b, z0, y0, x0, f): a window and the flip it is predicted under.  Bot
 prediction on the way back -- are index arithmetic inside the crop and the accumulate, so mirroring adds no pass over the data and
 no buffer; the accumulate is the store-and-sum form of blend.py (one launch per item in list order, no float atomics).
 """
-import ctypes
-
 import torch
 
-from . import _lib
+from . import _lib, blend
 
 # name -> argument signature (as _lib.SIGNATURES)
 SIGNATURES = {
@@ -40,21 +38,13 @@ def flip_codes(mirror_axes):
     return [f for f in range(8) if f & ~mask == 0]
 
 
-def _items(items):
-    arr = (ctypes.c_int32 * (5 * len(items)))()
-    for i, (b, z, y, x, f) in enumerate(items):
-        arr[5 * i:5 * i + 5] = [b, z, y, x, f]
-    return arr
-
-
 def window_batch(vol, items, roi):
     """vol [B, C, D, H, W]; items: a list of (b, z0, y0, x0, flip) -> [n, C, rd, rh, rw], window i cropped at its origin and reversed
     along the axes of its flip code; ONE launch."""
     B, C, D, H, W = vol.shape
     rd, rh, rw = roi
     win = torch.empty((len(items), C, rd, rh, rw), dtype=torch.float32, device=vol.device)
-    arr = _items(items)
-    _lib.call("micf_sw_mirror_window_batch", _lib.f32(vol), _lib.f32(win), ctypes.cast(arr, ctypes.c_void_p), len(items), B, C, D, H, W,
+    _lib.call("micf_sw_mirror_window_batch", _lib.f32(vol), _lib.f32(win), _lib.int32_rows(items, 5), len(items), B, C, D, H, W,
               rd, rh, rw)
     return win
 
@@ -63,15 +53,7 @@ def accumulate(pred, out, wsum, items, taps=None, floor=1.0):
     """pred [n, K, rd, rh, rw], prediction i flipped back by its item's code and weighted into out [B, K, D, H, W] and wsum
     [B, D, H, W] at the item's window: one launch per item in list order, no atomics.  taps / floor: blend.device_taps(), or None
     for a weight of 1 (include/micformer_mirror.h)."""
-    B, K, D, H, W = out.shape
-    rd, rh, rw = pred.shape[2:]
-    if pred.shape[0] != len(items) or pred.shape[1] != K or tuple(wsum.shape) != (B, D, H, W) or \
-            (taps is not None and taps.numel() != rd + rh + rw):
-        raise ValueError(f"mirror.accumulate: pred {tuple(pred.shape)}, out {tuple(out.shape)}, wsum {tuple(wsum.shape)}, "
-                         f"{len(items)} items and {'no' if taps is None else taps.numel()} taps do not fit together")
-    arr = _items(items)
-    _lib.call("micf_sw_mirror_accumulate", _lib.f32(pred), _lib.f32(out), _lib.f32(wsum), ctypes.cast(arr, ctypes.c_void_p),
-              len(items), B, K, D, H, W, rd, rh, rw, _lib.f32(taps), floor)
+    blend.store_and_sum("micf_sw_mirror_accumulate", 5, pred, out, wsum, items, taps, floor)
 
 
 def mirrored_logits(model, x, mirror_axes):
@@ -98,12 +80,9 @@ def mirrored_logits(model, x, mirror_axes):
             if out is None:
                 if pred.dim() != 5 or pred.shape[0] != B or tuple(pred.shape[2:]) != (D, H, W):
                     raise ValueError(f"model returned {tuple(pred.shape)} for an input of {tuple(image.shape)}")
-                out, wsum = torch.empty_like(pred), torch.empty((B, D, H, W), dtype=torch.float32, device=image.device)
-                _lib.call("micf_zero", _lib.ptr(out), out.numel() * 4)
-                _lib.call("micf_zero", _lib.ptr(wsum), wsum.numel() * 4)
+                out, wsum = blend.new_sums(B, pred.shape[1], D, H, W, image.device)
             accumulate(pred, out, wsum, items)
-        for b in range(B):
-            _lib.call("micf_sw_normalize", _lib.f32(out[b]), _lib.f32(wsum[b]), out.shape[1], D * H * W)
+        blend.normalize(out, wsum)
     return out
 
 

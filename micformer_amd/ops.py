@@ -1286,20 +1286,12 @@ def block_bwd(groups, dims, C, heads, scale):
 
 
 # ----------------------------------------------------------------------------- sliding window (batched) / input pipeline
-def _coords(chunk):
-    arr = (ctypes.c_int32 * (4 * len(chunk)))()
-    for i, (b, z, y, x) in enumerate(chunk):
-        arr[4 * i:4 * i + 4] = [b, z, y, x]
-    return arr
-
-
 def sw_window_batch(vol, chunk, roi):
     """vol [B, C, D, H, W]; chunk: list of (b, z0, y0, x0) -> [n, C, rd, rh, rw] crops, ONE launch."""
     B, C, D, H, W = vol.shape
     rd, rh, rw = roi
     win = _new(vol, len(chunk), C, rd, rh, rw)
-    arr = _coords(chunk)
-    call("micf_sw_window_batch", f32(vol), f32(win), ctypes.cast(arr, ctypes.c_void_p), len(chunk), B, C, D, H, W, rd, rh, rw)
+    call("micf_sw_window_batch", f32(vol), f32(win), _lib.int32_rows(chunk, 4), len(chunk), B, C, D, H, W, rd, rh, rw)
     return win
 
 
@@ -1307,9 +1299,7 @@ def sw_accumulate_batch(pred, out, count, chunk):
     """pred [n, K, rd, rh, rw] added into out [B, K, D, H, W] at the windows of `chunk`, count [B, D, H, W] += 1 there; ONE launch."""
     B, K, D, H, W = out.shape
     rd, rh, rw = pred.shape[2:]
-    arr = _coords(chunk)
-    call("micf_sw_accumulate_batch", f32(pred), f32(out), f32(count), ctypes.cast(arr, ctypes.c_void_p), len(chunk), B, K, D, H, W,
-         rd, rh, rw)
+    call("micf_sw_accumulate_batch", f32(pred), f32(out), f32(count), _lib.int32_rows(chunk, 4), len(chunk), B, K, D, H, W, rd, rh, rw)
 
 
 def intensity_stats(vol):

@@ -1,4 +1,4 @@
-"""Sliding-window inference with Gaussian blending on the device (micformer_amd.inference mode="gaussian", csrc/sw_blend.hip) against
+"""Sliding-window inference with Gaussian blending on the device (micformer_amd.inference mode="gaussian", csrc/sliding_window.hip) against
 the float64 referee of tests/sw_blend_ref.py fed the DEVICE's own per-window predictions.
 
 The synthetic predictor is dyadic (every value exact in float32 on either side), so the only error is the blend's, and the bound is
@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import sw_blend_ref as S
+from sw_head import filled_head as _head
 
 pytestmark = pytest.mark.gpu
 
@@ -129,16 +130,6 @@ def test_importance_map_on_the_device_is_the_host_map():
     _need_gpu()
     from micformer_amd.inference import importance_map
     assert torch.equal(importance_map((16, 24, 8), "gaussian", 0.125, device="cuda").cpu(), S.importance_map((16, 24, 8))[0])
-
-
-def _head(E, depths):
-    from oracle import fill
-    import micformer_amd.models.MICFormer_self as M
-    head = M.Head(embed_dim=E, num_classes=8, depths=depths)
-    with torch.no_grad():
-        for name, t in head.state_dict().items():
-            t.copy_(fill.fill_tensor(name, t))
-    return head.cuda().eval()
 
 
 def test_tiny_head_as_predictor_eager_graph_and_no_fused_epilogue():

@@ -1,4 +1,4 @@
-"""Test-time mirroring on the device (micformer_amd.inference mirror_axes=, micformer_amd/mirror.py, csrc/sw_mirror.hip) against the
+"""Test-time mirroring on the device (micformer_amd.inference mirror_axes=, micformer_amd/mirror.py, csrc/sliding_window.hip) against the
 float64 referee of tests/sw_mirror_ref.py fed the DEVICE's own per-item predictions.
 
 The synthetic predictor is dyadic (every value exact in float32 on either side) and not flip-equivariant (its ramps run in window
@@ -15,6 +15,7 @@ import torch
 
 import sw_blend_ref as S
 import sw_mirror_ref as M
+from sw_head import filled_head as _head
 
 pytestmark = pytest.mark.gpu
 
@@ -228,16 +229,6 @@ def test_a_pointwise_predictor_gives_the_unmirrored_result(mode):
     err = float((got.cpu().double() - ref).abs().max())
     print(f"pointwise {mode}: F {F}, error {err:.3g}, bound {bound:.3g}")
     assert F == 8 and err <= bound
-
-
-def _head(E, depths):
-    from oracle import fill
-    import micformer_amd.models.MICFormer_self as MF
-    head = MF.Head(embed_dim=E, num_classes=8, depths=depths)
-    with torch.no_grad():
-        for name, t in head.state_dict().items():
-            t.copy_(fill.fill_tensor(name, t))
-    return head.cuda().eval()
 
 
 @pytest.mark.parametrize("mode", MODES)

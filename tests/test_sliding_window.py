@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import micformer_ref as R
+from sw_head import filled_head as _head
 
 
 @pytest.mark.parametrize("L,roi,overlap", [(128, 128, 0.5), (100, 128, 0.5), (256, 128, 0.5), (512, 128, 0.5), (200, 128, 0.5),
@@ -81,16 +82,6 @@ def test_tiny_head_as_predictor_matches_oracle():
     assert float((got.cpu() - want).abs().max()) <= 1e-4
     assert torch.equal(got.argmax(1).cpu(), want.argmax(1)) or \
         float((got.argmax(1).cpu() != want.argmax(1)).float().mean()) < 1e-3
-
-
-def _head(E, depths):
-    from oracle import fill
-    import micformer_amd.models.MICFormer_self as M
-    head = M.Head(embed_dim=E, num_classes=8, depths=depths)
-    with torch.no_grad():
-        for name, t in head.state_dict().items():
-            t.copy_(fill.fill_tensor(name, t))
-    return head.cuda().eval()
 
 
 @pytest.mark.gpu

@@ -196,7 +196,7 @@ def test_header_table_binding_and_library_agree():
     batch = abi_header.parse_header("micformer_hip.h")["micf_sw_accumulate_batch"][1]
     assert d["micf_sw_blend_accumulate"][1] == batch[:-1] + "pf" + batch[-1]
     build = abi_header.build_module()
-    assert "sw_blend.hip" in build.SOURCES
+    assert "sliding_window.hip" in build.SOURCES
 
 
 def test_table_is_disjoint_from_the_others_and_the_main_table_is_untouched():

@@ -154,7 +154,7 @@ def test_header_table_binding_and_library_agree():
     assert d["micf_sw_mirror_window_batch"][1] == main["micf_sw_window_batch"][1]
     assert d["micf_sw_mirror_accumulate"][1] == abi_header.parse_header("micformer_blend.h")["micf_sw_blend_accumulate"][1]
     build = abi_header.build_module()
-    assert "sw_mirror.hip" in build.SOURCES and "sw_blend.hip" in build.SOURCES
+    assert "sliding_window.hip" in build.SOURCES
 
 
 def test_table_is_disjoint_from_the_others_and_the_main_table_is_untouched():
@@ -166,8 +166,10 @@ def test_table_is_disjoint_from_the_others_and_the_main_table_is_untouched():
 
 
 def test_kernels_use_no_scratch():
-    sizes, _, _ = abi_header.device_asm("sw_mirror.hip")
-    assert len(sizes) == 5 and all("sw_mirror" in k for k in sizes), sorted(sizes)      # the crop, and 2 row forms x taps / no taps
+    sizes, _, _ = abi_header.device_asm("sliding_window.hip")
+    # the crop, the store-and-sum accumulate in 2 row forms x taps / no taps x flip / no flip, the atomic accumulate, the normalise
+    assert len(sizes) == 11 and all("sw_" in k for k in sizes), sorted(sizes)
+    assert sum("sw_accumulate_kernel" in k for k in sizes) == 8 and sum("sw_crop_kernel" in k for k in sizes) == 1
     assert set(sizes.values()) == {0}, sizes
 
 
