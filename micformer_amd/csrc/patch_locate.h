@@ -2,7 +2,8 @@
 // volume_patch_warp.hip (the crop through a map): the view of an index buffer, the workgroup prefix, patch_locate_kernel, and the
 // host-side checks of the samples and their indexes.  Moved here from volume_patches.hip with its text unchanged.  Unnamed
 // namespace: each including file gets its own copy of the kernel, so both entry points launch the very same code and a draw gives
-// the same origin and pick through either.
+// the same origin and pick through either.  The launch itself, and everything else the two `sample` entries share, is
+// patch_sample_common.h's.
 #pragma once
 #include "volume_normalise_stats.h"
 #include "patches_coords.h"

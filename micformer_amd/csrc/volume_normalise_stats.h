@@ -395,12 +395,23 @@ __global__ __launch_bounds__(64) void norm_finish_kernel(MinMaxArgs a, Modes md,
 // The normaliser of one channel: one raw element -> its normalised fp32 value (micformer_normalise.h has the three rules).
 struct NormAny { int mode; Norm mm; float a, b, scale; };
 
-template <bool F32>
-__device__ __forceinline__ float tap(const void* p, int64_t off, const NormAny& nm) {
-  if (nm.mode == MICF_NORM_MINMAX) return tap<F32>(p, off, nm.mm);    // (feeds the crop extents only: see the launch plan)
-  const float x = F32 ? static_cast<const float*>(p)[off] : (float)(int)static_cast<const int16_t*>(p)[off];
+// the z-score and percentile-clip rules on a value already in fp32
+__device__ __forceinline__ float norm_f32(float x, const NormAny& nm) {
   if (nm.mode == MICF_NORM_ZSCORE) return x != 0.0f ? (x - nm.a) / nm.b : 0.0f;
   return (fminf(fmaxf(x, nm.a), nm.b) - nm.a) / nm.scale;             // numpy.clip = minimum(maximum(x, low), high)
+}
+
+// one raw int16 element already in a register (the patch crop unpacks eight of them from two vector loads)
+__device__ __forceinline__ float norm_i16(int x, const NormAny& nm) {
+  if (nm.mode == MICF_NORM_MINMAX) return (float)(x - nm.mm.imin) / nm.mm.scale;     // tap<false>(.., Norm)'s expression
+  return norm_f32((float)x, nm);
+}
+
+template <bool F32>
+__device__ __forceinline__ float tap(const void* p, int64_t off, const NormAny& nm) {
+  if constexpr (!F32) return norm_i16((int)static_cast<const int16_t*>(p)[off], nm);
+  else if (nm.mode == MICF_NORM_MINMAX) return tap<true>(p, off, nm.mm);     // (feeds the crop extents only: see the launch plan)
+  else return norm_f32(static_cast<const float*>(p)[off], nm);
 }
 
 struct NormWords {

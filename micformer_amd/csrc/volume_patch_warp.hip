@@ -2,9 +2,11 @@
 // patch coordinate n is moved by a displacement field interpolated on the patch grid, u, mapped by theta, s = theta . (n + u, 1),
 // turned into a scan index by the origin add, i = o + ((s + 1) P - 1) / 2, and the raw CT / MR / label arrays are read there: the
 // image interpolated once, the label rounded once, nothing intermediate written and nothing padded that the scan could have filled.
-// The locate step is patch_locate.h's kernel, the one volume_patches.hip launches; the map's arithmetic is affine_coords.h's, the
-// control grid's elastic_coords.h's, the origin add, the label's outside rule and the field's columns patch_warp_coords.h's (all
-// host-callable); the 8 normalised taps are affine_taps.h's affine_trilinear with the statistics of the scan's index.
+// The locate step is patch_locate.h's kernel, the one volume_patches.hip launches; the shared argument checks and the chunk driver
+// that launches it are patch_sample_common.h's (check_sample_call, sample_chunks); here are this entry's own checks, the warp
+// kernel and its launch.  The map's arithmetic is affine_coords.h's, the control grid's elastic_coords.h's, the origin add, the
+// label's outside rule and the field's columns patch_warp_coords.h's (all host-callable); the 8 normalised taps are affine_taps.h's
+// affine_trilinear with the statistics of the scan's index.
 //
 // Launch plan of micf_patch_sample_warped, per chunk of 8 samples:
 //   1 locate     patch_locate_kernel, unchanged: writes origins and picked
@@ -21,7 +23,7 @@
 // arrays or the field.  Nothing crosses threads but theta through LDS: bit-identical from run to run, independent of the other
 // samples.  No scratch, no workspace, no atomics.
 #include "affine_taps.h"
-#include "patch_locate.h"
+#include "patch_sample_common.h"
 #include "patch_warp_coords.h"
 #include "../../include/micformer_patch_warp.h"
 
@@ -149,21 +151,6 @@ __global__ __launch_bounds__(kThreads) void patch_warp_kernel(ResizeArgs a, Inde
   }
 }
 
-template <int kPer>
-void launch_warp(int taps, dim3 grid, hipStream_t s, const ResizeArgs& ra, const IndexArgs& ia, const int32_t* origins, int Pd, int Ph,
-                 int Pw, const float* theta, int per_modality, const float* field, int gd, int gh, int gw, int border, int pad_class,
-                 __half* image, uint8_t* label_map) {
-  if (taps == 0)
-    hipLaunchKernelGGL((patch_warp_kernel<kPer, 0>), grid, dim3(kThreads), 0, s, ra, ia, origins, Pd, Ph, Pw, theta, per_modality, field,
-                       gd, gh, gw, border, pad_class, image, label_map);
-  else if (taps == 2)
-    hipLaunchKernelGGL((patch_warp_kernel<kPer, 2>), grid, dim3(kThreads), 0, s, ra, ia, origins, Pd, Ph, Pw, theta, per_modality, field,
-                       gd, gh, gw, border, pad_class, image, label_map);
-  else
-    hipLaunchKernelGGL((patch_warp_kernel<kPer, 4>), grid, dim3(kThreads), 0, s, ra, ia, origins, Pd, Ph, Pw, theta, per_modality, field,
-                       gd, gh, gw, border, pad_class, image, label_map);
-}
-
 }  // namespace
 
 extern "C" int micf_patch_sample_warped(const micf_loader_sample* samples, int B, void* const* indexes, const int64_t* index_bytes,
@@ -171,57 +158,41 @@ extern "C" int micf_patch_sample_warped(const micf_loader_sample* samples, int B
                                         int padding_mode, int pad_class, int clamp, void* image, uint8_t* label_map, int32_t* origins,
                                         int32_t* picked, const float* affine, int affine_per_modality, const float* displacement,
                                         int gd, int gh, int gw, int field_interpolation, micf_stream_t stream) {
-  if (!samples || !indexes || !index_bytes || !draws || !image || !origins || !picked || B <= 0 || Pd <= 0 || Ph <= 0 || Pw <= 0)
-    return MICF_EINVAL;
-  if (padding_mode != MICF_PATCH_PAD_ZEROS && padding_mode != MICF_PATCH_PAD_BORDER) return MICF_EINVAL;
-  if (clamp != MICF_PATCH_CLAMP_BOTH && clamp != MICF_PATCH_CLAMP_LOWER) return MICF_EINVAL;
-  if (pad_class < 0 || pad_class > 255) return MICF_EINVAL;
+  // this entry's own MICF_EINVAL checks, then the shared ones, then its own MICF_EUNSUPPORTED limit
   if ((reinterpret_cast<uintptr_t>(affine) & 3) || (reinterpret_cast<uintptr_t>(displacement) & 3)) return MICF_EINVAL;
   if (affine_per_modality != 0 && affine_per_modality != 1) return MICF_EINVAL;
   if (displacement) {
     if (field_interpolation != MICF_FIELD_LINEAR && field_interpolation != MICF_FIELD_CUBIC) return MICF_EINVAL;
     if (gd < 2 || gh < 2 || gw < 2) return MICF_EINVAL;
   }
-  int rc = check_label_values(label_values, num_label_values);
-  if (rc != MICF_OK) return rc;
+  const SampleCall c{samples, B, indexes, index_bytes, label_values, num_label_values, draws, Pd, Ph, Pw, padding_mode, pad_class, clamp,
+                     image, label_map, origins, picked};
   const int per = Pw % 8 == 0 ? 8 : (Pw % 4 == 0 ? 4 : 1);
-  if (reinterpret_cast<uintptr_t>(image) & (uintptr_t)(2 * per - 1)) return MICF_EINVAL;
-  if (reinterpret_cast<uintptr_t>(label_map) & (uintptr_t)(per - 1)) return MICF_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(draws) & 3) || (reinterpret_cast<uintptr_t>(origins) & 3) || (reinterpret_cast<uintptr_t>(picked) & 3))
-    return MICF_EINVAL;
-  rc = check_scans(samples, B, label_map != nullptr, num_label_values, indexes, index_bytes);
+  const int rc = check_sample_call(c, per);
   if (rc != MICF_OK) return rc;
-  if ((int64_t)Pd * Ph > kMaxTarget || (int64_t)Pd * Ph * Pw > kMaxTarget) return MICF_EUNSUPPORTED;
   if (displacement && (gd > kMaxGrid || gh > kMaxGrid || gw > kMaxGrid)) return MICF_EUNSUPPORTED;
 
   hipStream_t s = (hipStream_t)stream;
-  const int64_t V = (int64_t)Pd * Ph * Pw;
   const int nth = affine_per_modality ? 24 : 12;
   const int taps = !displacement ? 0 : (field_interpolation == MICF_FIELD_CUBIC ? 4 : 2);
   const size_t per_field = displacement ? (size_t)3 * gd * gh * gw : 0;
   const int border = padding_mode == MICF_PATCH_PAD_BORDER ? 1 : 0;
-  MinMaxArgs ma;
-  ResizeArgs ra;
-  fill_label_values(ra, label_values, num_label_values);
-  for_each_chunk(samples, B, ma, ra, [&](int b0, int nb, unsigned) {
-    IndexArgs ia;
-    fill_indexes(ia, indexes, b0, nb);
-    hipLaunchKernelGGL(patch_locate_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, ra, ia, draws + (size_t)b0 * 6, Pd, Ph, Pw,
-                       label_map ? 1 : 0, clamp == MICF_PATCH_CLAMP_LOWER ? 1 : 0, origins + (size_t)b0 * 3, picked + (size_t)b0 * 4);
-    __half* img0 = static_cast<__half*>(image) + (size_t)b0 * 2 * V;
-    uint8_t* lab0 = label_map ? label_map + (size_t)b0 * V : nullptr;
+  sample_chunks(c, per, s, [&](dim3 grid, const ResizeArgs& ra, const IndexArgs& ia, const int32_t* org, __half* img0, uint8_t* lab0,
+                               int b0) {
     const float* th0 = affine ? affine + (size_t)b0 * nth : nullptr;
     const float* fl0 = displacement ? displacement + (size_t)b0 * per_field : nullptr;
-    const dim3 grid(resize_blocks(V / per), (unsigned)nb);
-    if (per == 8)
-      launch_warp<8>(taps, grid, s, ra, ia, origins + (size_t)b0 * 3, Pd, Ph, Pw, th0, affine_per_modality, fl0, gd, gh, gw, border,
-                     pad_class, img0, lab0);
-    else if (per == 4)
-      launch_warp<4>(taps, grid, s, ra, ia, origins + (size_t)b0 * 3, Pd, Ph, Pw, th0, affine_per_modality, fl0, gd, gh, gw, border,
-                     pad_class, img0, lab0);
-    else
-      launch_warp<1>(taps, grid, s, ra, ia, origins + (size_t)b0 * 3, Pd, Ph, Pw, th0, affine_per_modality, fl0, gd, gh, gw, border,
-                     pad_class, img0, lab0);
+    const auto launch = [&](auto kper, auto ktaps) {
+      hipLaunchKernelGGL((patch_warp_kernel<decltype(kper)::value, decltype(ktaps)::value>), grid, dim3(kThreads), 0, s, ra, ia, org,
+                         Pd, Ph, Pw, th0, affine_per_modality, fl0, gd, gh, gw, border, pad_class, img0, lab0);
+    };
+    const auto with_taps = [&](auto kper) {
+      if (taps == 0) launch(kper, Int<0>{});
+      else if (taps == 2) launch(kper, Int<2>{});
+      else launch(kper, Int<4>{});
+    };
+    if (per == 8) with_taps(Int<8>{});
+    else if (per == 4) with_taps(Int<4>{});
+    else with_taps(Int<1>{});
   });
   MICF_RETURN_LAUNCH();
 }

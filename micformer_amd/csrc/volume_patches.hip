@@ -21,7 +21,7 @@
 //                then reads that segment's 2048 labels in 8 rounds, a ballot + popcount per wave and round gives 32 ordered
 //                counts, and the lane whose match has the wanted number of matches below it writes origins and picked.  An index
 //                that does not fit its scan (the rank is never found) falls back to the random crop: no address depends on it.
-//   2 crop       patch_crop_kernel, grid (blocks, samples), the only bandwidth path: reads origins from device memory; a thread
+//   2 crop       patch_crop_kernel<kPer>, grid (blocks, samples), the only bandwidth path: reads origins from device memory; a thread
 //                makes 8 consecutive output voxels of a row (Pw % 8 == 0: one 16-byte store per channel, one 8-byte store of
 //                classes) or one voxel (any Pw).  Source rows start at an arbitrary element offset: where the 8 positions
 //                lie inside one row of int16 arrays, each array is read with two aligned 16-byte loads and shifted by the byte
@@ -29,9 +29,11 @@
 //                arrays, groups that cross the scan's border or touch the array's last bytes -- per element, every index
 //                clamped into the scan before it is used.
 // Everything that crosses threads is an integer: bit-identical from run to run, independent of the other samples.  No scratch.
-// The locate kernel, the view of an index buffer and the host-side checks of the scans live in patch_locate.h, which
-// volume_patch_warp.hip shares.
-#include "patch_locate.h"
+// The locate kernel, the view of an index buffer and the host-side checks of the scans live in patch_locate.h; the argument checks
+// of micf_patch_sample and the chunk driver with the locate launch, which micf_patch_sample_warped (volume_patch_warp.hip) shares,
+// in patch_sample_common.h (check_sample_call, sample_chunks).  norm_i16, the normaliser of an element already in a register, is
+// volume_normalise_stats.h's, where tap<false> is the load followed by it.
+#include "patch_sample_common.h"
 
 namespace {
 
@@ -91,14 +93,6 @@ __device__ __forceinline__ float norm_tap(const Vol3& v, bool f32, int64_t off, 
   return f32 ? tap<true>(v.p, off, nm) : tap<false>(v.p, off, nm);
 }
 
-// The normalised value of one raw int16 element: tap<false>'s arithmetic on a value already in a register.
-__device__ __forceinline__ float norm_i16(int x, const NormAny& nm) {
-  if (nm.mode == MICF_NORM_MINMAX) return (float)(x - nm.mm.imin) / nm.mm.scale;
-  const float f = (float)x;
-  if (nm.mode == MICF_NORM_ZSCORE) return f != 0.0f ? (f - nm.a) / nm.b : 0.0f;
-  return (fminf(fmaxf(f, nm.a), nm.b) - nm.a) / nm.scale;
-}
-
 // Elements [off, off + 8) of an int16 volume of n elements through two aligned 16-byte loads and a shift by the byte offset of
 // the first element; false (nothing loaded) where the two vectors do not lie inside the volume.
 __device__ __forceinline__ bool shifted8_i16(const void* p, int64_t n, int64_t off, uint32_t (&out)[4]) {
@@ -118,8 +112,8 @@ __device__ __forceinline__ int unpack_i16(const uint32_t (&v)[4], int j) {
   return (int)(int16_t)((v[j / 2] >> (16 * (j & 1))) & 0xFFFFu);
 }
 
-// grid (blocks, samples of the chunk); origins / image / label_map point at the chunk's first sample
-template <bool kVec>
+// grid (blocks, samples of the chunk); origins / image / label_map point at the chunk's first sample; kPer 8 or 1 outputs per thread
+template <int kPer>
 __global__ __launch_bounds__(kThreads) void patch_crop_kernel(ResizeArgs a, IndexArgs ia, const int32_t* origins, int Pd, int Ph, int Pw,
                                                               int border, int pad_class, __half* image, uint8_t* label_map) {
   const SampleDesc& sd = a.s[blockIdx.y];
@@ -131,53 +125,44 @@ __global__ __launch_bounds__(kThreads) void patch_crop_kernel(ResizeArgs a, Inde
   const int V = Pd * Ph * Pw;
   __half* img = image + (size_t)blockIdx.y * 2 * V;
   uint8_t* lab = label_map ? label_map + (size_t)blockIdx.y * V : nullptr;
-  constexpr int kPer = kVec ? 8 : 1;
   const int groups = Pw / kPer, items = Pd * Ph * groups;
   for (int item = blockIdx.x * kThreads + threadIdx.x; item < items; item += gridDim.x * kThreads) {
     const int xg = item % groups, row = item / groups, y = row % Ph, z = row / Ph;
     const int sz = oz + z, sy = oy + y;
     const bool in_zy = pc::inside(sz, d) && pc::inside(sy, h);
     const int64_t rowoff = ((int64_t)pc::clamp_index(sz, d) * h + pc::clamp_index(sy, h)) * w;
-    uint32_t h0[kVec ? 4 : 1] = {}, h1[kVec ? 4 : 1] = {}, cl[kVec ? 2 : 1] = {};
-    if (kVec) {                                                  // the 8 positions lie in one source row: two vector loads per array
-      const int sx0 = ox + xg * kPer;
-      uint32_t r0[4], r1[4], rl[4];
-      if (sx0 >= 0 && sx0 + kPer <= w && (in_zy || border) && !ct32 && !mr32 && (!lab || sd.lab.dtype == MICF_LOADER_I16) &&
-          shifted8_i16(sd.ct.p, (int64_t)d * h * w, rowoff + sx0, r0) && shifted8_i16(sd.mr.p, (int64_t)d * h * w, rowoff + sx0, r1) &&
-          (!lab || !in_zy || shifted8_i16(sd.lab.p, (int64_t)d * h * w, rowoff + sx0, rl))) {
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) {
-          const float c0 = norm_i16(unpack_i16(r0, j), nct), c1 = norm_i16(unpack_i16(r1, j), nmr);
-          const int c = (lab && in_zy) ? label_class(a, unpack_i16(rl, j)) : pad_class;
-          h0[j / 2] |= (uint32_t)__half_as_ushort(__float2half_rn(c0)) << (16 * (j & 1));
-          h1[j / 2] |= (uint32_t)__half_as_ushort(__float2half_rn(c1)) << (16 * (j & 1));
-          cl[j / 4] |= (uint32_t)c << (8 * (j & 3));
-        }
-        const int o = row * Pw + xg * kPer;
-        *reinterpret_cast<uint4*>(img + o) = make_uint4(h0[0], h0[1], h0[2], h0[3]);
-        *reinterpret_cast<uint4*>(img + (size_t)V + o) = make_uint4(h1[0], h1[1], h1[2], h1[3]);
-        if (lab) *reinterpret_cast<uint2*>(lab + o) = make_uint2(cl[0], cl[1]);
-        continue;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-      const int sx = ox + xg * kPer + j;
-      const bool in = in_zy && pc::inside(sx, w);
-      const int64_t off = rowoff + pc::clamp_index(sx, w);
-      float c0 = 0.0f, c1 = 0.0f;
-      if (in || border) {
-        c0 = norm_tap(sd.ct, ct32, off, nct);
-        c1 = norm_tap(sd.mr, mr32, off, nmr);
-      }
-      int c = pad_class;
-      if (lab && in) c = label_class(a, raw_label(sd.lab, off));
+    uint32_t h0[kPer > 1 ? kPer / 2 : 1] = {}, h1[kPer > 1 ? kPer / 2 : 1] = {}, cl[kPer > 4 ? 2 : 1] = {};
+    const auto put = [&](int j, float c0, float c1, int c) {
       h0[j / 2] |= (uint32_t)__half_as_ushort(__float2half_rn(c0)) << (16 * (j & 1));
       h1[j / 2] |= (uint32_t)__half_as_ushort(__float2half_rn(c1)) << (16 * (j & 1));
       cl[j / 4] |= (uint32_t)c << (8 * (j & 3));
+    };
+    const int sx0 = ox + xg * kPer;
+    uint32_t r0[4], r1[4], rl[4];
+    // the 8 positions lie in one source row: two vector loads per array
+    if (kPer == 8 && sx0 >= 0 && sx0 + kPer <= w && (in_zy || border) && !ct32 && !mr32 && (!lab || sd.lab.dtype == MICF_LOADER_I16) &&
+        shifted8_i16(sd.ct.p, (int64_t)d * h * w, rowoff + sx0, r0) && shifted8_i16(sd.mr.p, (int64_t)d * h * w, rowoff + sx0, r1) &&
+        (!lab || !in_zy || shifted8_i16(sd.lab.p, (int64_t)d * h * w, rowoff + sx0, rl))) {
+#pragma unroll
+      for (int j = 0; j < kPer; ++j)
+        put(j, norm_i16(unpack_i16(r0, j), nct), norm_i16(unpack_i16(r1, j), nmr),
+            (lab && in_zy) ? label_class(a, unpack_i16(rl, j)) : pad_class);
+    } else {
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) {
+        const int sx = sx0 + j;
+        const bool in = in_zy && pc::inside(sx, w);
+        const int64_t off = rowoff + pc::clamp_index(sx, w);
+        float c0 = 0.0f, c1 = 0.0f;
+        if (in || border) {
+          c0 = norm_tap(sd.ct, ct32, off, nct);
+          c1 = norm_tap(sd.mr, mr32, off, nmr);
+        }
+        put(j, c0, c1, lab && in ? label_class(a, raw_label(sd.lab, off)) : pad_class);
+      }
     }
     const int o = row * Pw + xg * kPer;
-    if (kVec) {
+    if constexpr (kPer == 8) {
       *reinterpret_cast<uint4*>(img + o) = make_uint4(h0[0], h0[1], h0[2], h0[3]);
       *reinterpret_cast<uint4*>(img + (size_t)V + o) = make_uint4(h1[0], h1[1], h1[2], h1[3]);
       if (lab) *reinterpret_cast<uint2*>(lab + o) = make_uint2(cl[0], cl[1]);
@@ -244,41 +229,20 @@ extern "C" int micf_patch_sample(const micf_loader_sample* samples, int B, void*
                                  const int32_t* label_values, int num_label_values, const float* draws, int Pd, int Ph, int Pw,
                                  int padding_mode, int pad_class, int clamp, void* image, uint8_t* label_map, int32_t* origins,
                                  int32_t* picked, micf_stream_t stream) {
-  if (!samples || !indexes || !index_bytes || !draws || !image || !origins || !picked || B <= 0 || Pd <= 0 || Ph <= 0 || Pw <= 0)
-    return MICF_EINVAL;
-  if (padding_mode != MICF_PATCH_PAD_ZEROS && padding_mode != MICF_PATCH_PAD_BORDER) return MICF_EINVAL;
-  if (clamp != MICF_PATCH_CLAMP_BOTH && clamp != MICF_PATCH_CLAMP_LOWER) return MICF_EINVAL;
-  if (pad_class < 0 || pad_class > 255) return MICF_EINVAL;
-  int rc = check_label_values(label_values, num_label_values);
+  const SampleCall c{samples, B, indexes, index_bytes, label_values, num_label_values, draws, Pd, Ph, Pw, padding_mode, pad_class, clamp,
+                     image, label_map, origins, picked};
+  const int per = Pw % 8 == 0 ? 8 : 1;
+  const int rc = check_sample_call(c, per);
   if (rc != MICF_OK) return rc;
-  const bool vec = Pw % 8 == 0;
-  if (reinterpret_cast<uintptr_t>(image) & (vec ? 15 : 1)) return MICF_EINVAL;
-  if (vec && (reinterpret_cast<uintptr_t>(label_map) & 7)) return MICF_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(draws) & 3) || (reinterpret_cast<uintptr_t>(origins) & 3) || (reinterpret_cast<uintptr_t>(picked) & 3))
-    return MICF_EINVAL;
-  rc = check_scans(samples, B, label_map != nullptr, num_label_values, indexes, index_bytes);
-  if (rc != MICF_OK) return rc;
-  if ((int64_t)Pd * Ph > kMaxTarget || (int64_t)Pd * Ph * Pw > kMaxTarget) return MICF_EUNSUPPORTED;
-
   hipStream_t s = (hipStream_t)stream;
-  const int64_t V = (int64_t)Pd * Ph * Pw;
-  MinMaxArgs ma;
-  ResizeArgs ra;
-  fill_label_values(ra, label_values, num_label_values);
-  for_each_chunk(samples, B, ma, ra, [&](int b0, int nb, unsigned) {
-    IndexArgs ia;
-    fill_indexes(ia, indexes, b0, nb);
-    hipLaunchKernelGGL(patch_locate_kernel, dim3((unsigned)nb), dim3(kThreads), 0, s, ra, ia, draws + (size_t)b0 * 6, Pd, Ph, Pw,
-                       label_map ? 1 : 0, clamp == MICF_PATCH_CLAMP_LOWER ? 1 : 0, origins + (size_t)b0 * 3, picked + (size_t)b0 * 4);
-    __half* img0 = static_cast<__half*>(image) + (size_t)b0 * 2 * V;
-    uint8_t* lab0 = label_map ? label_map + (size_t)b0 * V : nullptr;
-    const dim3 grid(resize_blocks(vec ? V / 8 : V), (unsigned)nb);
-    if (vec)
-      hipLaunchKernelGGL(patch_crop_kernel<true>, grid, dim3(kThreads), 0, s, ra, ia, origins + (size_t)b0 * 3, Pd, Ph, Pw,
-                         padding_mode == MICF_PATCH_PAD_BORDER ? 1 : 0, pad_class, img0, lab0);
-    else
-      hipLaunchKernelGGL(patch_crop_kernel<false>, grid, dim3(kThreads), 0, s, ra, ia, origins + (size_t)b0 * 3, Pd, Ph, Pw,
-                         padding_mode == MICF_PATCH_PAD_BORDER ? 1 : 0, pad_class, img0, lab0);
+  const int border = padding_mode == MICF_PATCH_PAD_BORDER ? 1 : 0;
+  sample_chunks(c, per, s, [&](dim3 grid, const ResizeArgs& ra, const IndexArgs& ia, const int32_t* org, __half* img0, uint8_t* lab0, int) {
+    const auto launch = [&](auto kper) {
+      hipLaunchKernelGGL(patch_crop_kernel<decltype(kper)::value>, grid, dim3(kThreads), 0, s, ra, ia, org, Pd, Ph, Pw, border, pad_class,
+                         img0, lab0);
+    };
+    if (per == 8) launch(Int<8>{});
+    else launch(Int<1>{});
   });
   MICF_RETURN_LAUNCH();
 }

@@ -164,16 +164,24 @@ def _mode(value, table, what):
     return table[value]
 
 
+def _typed_pad_class(pad_class):
+    if isinstance(pad_class, bool) or not isinstance(pad_class, int):
+        raise TypeError(f"pad_class must be an integer, got {type(pad_class).__name__}")
+
+
+def _typed_draws(draws):
+    if not isinstance(draws, torch.Tensor) or draws.dtype != torch.float32:
+        raise TypeError("draws must be a float32 tensor")
+
+
 def _typed(padding_mode, pad_class, clamp, draws):
     """The TypeError half of sample_patches' keyword checks, for a caller (patch_warp) that raises every TypeError of its own
     keywords before the first ValueError."""
     for value, table, what in ((padding_mode, PADDING_MODES, "padding_mode"), (clamp, CLAMPS, "clamp")):
         if not isinstance(value, str):
             _mode(value, table, what)
-    if isinstance(pad_class, bool) or not isinstance(pad_class, int):
-        raise TypeError(f"pad_class must be an integer, got {type(pad_class).__name__}")
-    if not isinstance(draws, torch.Tensor) or draws.dtype != torch.float32:
-        raise TypeError("draws must be a float32 tensor")
+    _typed_pad_class(pad_class)
+    _typed_draws(draws)
 
 
 def _prepare(samples, indexes, draws, patch_size, padding_mode, pad_class, clamp, out, what="sample_patches"):
@@ -182,12 +190,10 @@ def _prepare(samples, indexes, draws, patch_size, padding_mode, pad_class, clamp
     Pd, Ph, Pw = _args.triple(patch_size, "patch_size")
     pad = _mode(padding_mode, PADDING_MODES, "padding_mode")
     clamp_mode = _mode(clamp, CLAMPS, "clamp")
-    if isinstance(pad_class, bool) or not isinstance(pad_class, int):
-        raise TypeError(f"pad_class must be an integer, got {type(pad_class).__name__}")
+    _typed_pad_class(pad_class)
     if not 0 <= pad_class <= 255:
         raise ValueError(f"pad_class must lie in 0..255, got {pad_class}")
-    if not isinstance(draws, torch.Tensor) or draws.dtype != torch.float32:
-        raise TypeError("draws must be a float32 tensor")
+    _typed_draws(draws)
     items, device, has_label, meta = _describe(samples, what)
     B = len(meta)
     indexes = list(indexes)
