@@ -448,11 +448,7 @@ extern "C" int micf_window_attn_bwd(const float* q, int ldq, const float* k, con
 #undef MICF_BWD4
     MICF_RETURN_LAUNCH();
   }
-#define MICF_BWD(HD_) hipLaunchKernelGGL(wattn_bwd_kernel<HD_>, grid, dim3(256), 0, s, q, ldq, k, v, ldkv, d_o, ldo, dq, lddq, dk, dv, lddkv, g, scale, nwin)
-  if (vec && g.hd == 16) MICF_BWD(16);
-  else if (vec && g.hd == 8) MICF_BWD(8);
-  else if (vec && g.hd == 32) MICF_BWD(32);
-  else MICF_BWD(0);
-#undef MICF_BWD
+  // (unit_map cannot fail for N <= kMaxWin: hc = 1 gives N * lph <= 64 threads -- so every vector shape of head dim 8 / 16 / 32 left above)
+  hipLaunchKernelGGL(wattn_bwd_kernel<0>, grid, dim3(256), 0, s, q, ldq, k, v, ldkv, d_o, ldo, dq, lddq, dk, dv, lddkv, g, scale, nwin);
   MICF_RETURN_LAUNCH();
 }

@@ -95,7 +95,7 @@ def layernorm_bwd(dy, x1, mean, rstd, gamma, dgamma, dbeta, x2=None, add=None, d
     partials = None
     if defer is not None and x2 is None:
         nb = _lib.lib.micf_layernorm_bwd_partial_rows(rows, C, c1)
-        if nb > 0 and not ((dy.data_ptr() | x1.data_ptr() | gamma.data_ptr() | (add.data_ptr() if add is not None else 0)) & 15):
+        if nb > 0 and not ((dy.data_ptr() | x1.data_ptr() | gamma.data_ptr() | dx1.data_ptr() | (add.data_ptr() if add is not None else 0)) & 15):
             partials = _new(x1, nb, 2 * C)
             defer.append((partials, nb, C, dgamma, dbeta))
     call("micf_layernorm_bwd", f32(dy), f32(x1), f32(x2), c1, f32(mean), f32(rstd), f32(gamma), f32(dx1), f32(dx2),
@@ -127,6 +127,10 @@ def layernorm_bwd_pair(items, defers):
     arr = (_lib.LnBwdPairItem * 2)()
     outs = []
     nb = _lib.lib.micf_layernorm_bwd_partial_rows(rows, C, C)
+    # the partial form exists for the vector kernel only, and ONE operand of EITHER item off a 16-byte boundary turns the launch into two
+    # single calls, the misaligned one on the scalar kernel (micf_layernorm_bwd_pair's `ok`): decided here for the pair, before anything is queued
+    if nb > 0 and any(t is not None and t.data_ptr() & 15 for d in items for t in (d["x"], d["dy"], d["gamma"], d.get("add"), d.get("out"))):
+        nb = 0
     for it, d, defer in zip(arr, items, defers):
         dx = d.get("out") if d.get("out") is not None else _new(d["x"], rows, C)
         partials = None

@@ -1,6 +1,12 @@
 """GPU parity tests, op level: every C-ABI entry point against the CPU oracle / a plain PyTorch fp32 reference of the
 same op, on seeded inputs, forward and backward.  Tolerance: fp32 kernels vs fp32 CPU -> 2e-5 abs + 1e-4 of the
 tensor's max (atomically accumulated weight gradients: 2e-4 of max).  Run on the GPU box: pytest -m gpu.
+
+LayerNorm and window attention: this file runs the arms the model's common shapes take (the vector LayerNorm kernels <16,1> .. <64,2>
+and their deferred form, the window-attention instantiations for head dim 8 / 16 / 32 with one chunk per window, head dim 6 on the
+runtime kernels).  Every other host dispatch arm of layernorm.hip and window_attn.hip -- the scalar LayerNorm kernels, <64,4> and
+<64,8>, the pair entries, chunked backward units, window sizes below 8, the packed-qkv wrappers -- is in test_gpu_ln_attn_arms.py,
+against float64; its docstring maps arm to test.
 """
 import math
 import os
