@@ -403,7 +403,8 @@ int micf_dice_metric(const float* logits, const void* target, int target_is_labe
  * micf_adam_tick increments step and recomputes lr = eta_min + (base-eta_min)*(1+cos(pi*(step-1)/t_max))/2,
  * micf_adam_step applies the update with bias corrections for `step`; the gradient is read as grad_scale * g (1/world after a
  * sum all-reduce, 1 on one GPU).  p_bf16 (optional, n uint16_t): a bf16 (round-to-nearest-even) mirror of the updated
- * parameters, written in the same pass -- what the fused block kernels stream in bf16 mode, so no per-step conversion launch. */
+ * parameters, written in the same pass -- what the fused block kernels stream in bf16 mode, so no per-step conversion launch.
+ * n = 0 is a no-op (the buffer pointers may then be NULL); otherwise p, g, m, v 16-byte and p_bf16 8-byte aligned, else MICF_EINVAL. */
 int micf_adam_tick(void* state, double base_lr, double eta_min, int64_t t_max, micf_stream_t stream);
 int micf_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const void* state, float beta1,
                    float beta2, float eps, float grad_scale, void* p_bf16, micf_stream_t stream);

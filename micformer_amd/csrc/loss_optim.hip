@@ -284,8 +284,9 @@ extern "C" int micf_adam_tick(void* state, double base_lr, double eta_min, int64
 
 extern "C" int micf_adam_step(float* p, const float* g, float* m, float* v, int64_t n, const void* state, float beta1,
                               float beta2, float eps, float grad_scale, void* p_bf16, micf_stream_t stream) {
-  if (!p || !g || !m || !v || !state || n < 0) return MICF_EINVAL;
-  if (n == 0) return MICF_OK;
+  if (!state || n < 0) return MICF_EINVAL;
+  if (n == 0) return MICF_OK;                 // an empty range of the flat buffers: torch reports its pointers as NULL
+  if (!p || !g || !m || !v) return MICF_EINVAL;
   if (!aligned16(p) || !aligned16(g) || !aligned16(m) || !aligned16(v) || (reinterpret_cast<uintptr_t>(p_bf16) & 7)) return MICF_EINVAL;
   int blocks = (int)((n + 1023) / 1024);
   if (blocks > 4096) blocks = 4096;

@@ -871,7 +871,9 @@ def dice_bce_bwd(logits, target, sums, grad_out):
 
 
 def argmax_meandice(logits, label=None, want_mask=True):
-    """logits [B,K,...] fp32; label uint8 class map [B,...] or None.  Returns (mask uint8, meandice 0-d double or None)."""
+    """logits [B,K,...] fp32, K <= 32; label uint8 class map [B,...] or None.  Returns (mask uint8, meandice 0-d double or None).
+    The first maximum wins, as in torch.argmax; labels >= K are counted in no class.  NaN logits are outside the contract: the
+    kernel's `v > best` never selects a later NaN, torch.argmax does."""
     B, K = logits.shape[:2]
     V = logits[0, 0].numel()
     mask = torch.empty((B,) + tuple(logits.shape[2:]), dtype=torch.uint8, device=logits.device) if want_mask else None
@@ -885,7 +887,9 @@ def argmax_meandice(logits, label=None, want_mask=True):
 
 def dice_metric(logits, target):
     """MDiceLoss(_Val).metric on the device: [B, K] thresholded-sigmoid Dice per (sample, class); target = one-hot float planes
-    [B, K, ...] or a uint8 class map [B, ...]."""
+    [B, K, ...] or a uint8 class map [B, ...].  The threshold is z > 0.  The reference's fp32 sigmoid(z) > 0.5 is the same test except
+    for 0 < z <~ 1.2e-7 (below 1.5 * 2^-24 = 8.9e-8 with ATen's CPU sigmoid), where sigmoid(z) rounds to 0.5 and the reference calls
+    background what this kernel calls foreground; +0, -0 and every negative logit are background in both."""
     B, K = logits.shape[:2]
     V = logits[0, 0].numel()
     sums = _new(logits, B * K * 3, dtype=torch.float64)

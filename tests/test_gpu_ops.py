@@ -7,6 +7,10 @@ and their deferred form, the window-attention instantiations for head dim 8 / 16
 runtime kernels).  Every other host dispatch arm of layernorm.hip and window_attn.hip -- the scalar LayerNorm kernels, <64,4> and
 <64,8>, the pair entries, chunked backward units, window sizes below 8, the packed-qkv wrappers -- is in test_gpu_ln_attn_arms.py,
 against float64; its docstring maps arm to test.
+
+Loss, metrics and Adam (loss_optim.hip): this file runs one or two training shapes per kernel against the fp32 oracle.  Every other
+launch edge -- several chunks, the scalar-load fall-back, the grid caps, the bf16 mirror, sliced and empty Adam ranges -- is in
+test_gpu_loss_optim_edges.py, against the float64 referee loss_optim_ref.py with derived bounds; its docstring maps arm to test.
 """
 import math
 import os
