@@ -11,7 +11,7 @@ LIB = os.path.join(HERE, "libmicformer_hip.so")
 SOURCES = ["linear.hip", "linear_grouped.hip", "head_tail.hip", "head_tail_fused.hip", "layernorm.hip", "window_attn.hip", "conv3.hip", "conv3_wgrad.hip", "conv3_direct.hip", "conv3_fwdx.hip", "conv3_bwdx.hip", "conv3_wgradx.hip", "offset_sample.hip", "patch.hip",
            "loss_optim.hip", "misc.hip", "block_fwd.hip", "block_bwd.hip", "block_wide.hip", "offset_head.hip", "grad_wire.hip",
            "surface_metrics.hip", "surface_distance.hip", "volume_loader.hip", "volume_normalise.hip", "volume_affine.hip", "volume_elastic.hip", "volume_intensity.hip", "volume_restore.hip", "volume_components.hip",
-           "sliding_window.hip", "volume_patches.hip", "volume_patch_warp.hip"]
+           "sliding_window.hip", "volume_patches.hip", "volume_patch_warp.hip", "volume_lowres.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-fvisibility=default"]
 
 
@@ -40,6 +40,7 @@ def build_library(force=False, verbose=True):
     headers.append(os.path.join(os.path.dirname(HERE), "include", "micformer_affine.h"))
     headers.append(os.path.join(os.path.dirname(HERE), "include", "micformer_elastic.h"))
     headers.append(os.path.join(os.path.dirname(HERE), "include", "micformer_intensity.h"))
+    headers.append(os.path.join(os.path.dirname(HERE), "include", "micformer_lowres.h"))
     headers.append(os.path.join(os.path.dirname(HERE), "include", "micformer_restore.h"))
     headers.append(os.path.join(os.path.dirname(HERE), "include", "micformer_components.h"))
     headers.append(os.path.join(os.path.dirname(HERE), "include", "micformer_blend.h"))
